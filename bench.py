@@ -15,6 +15,11 @@ problem latency figures the reference reports (iterations/s of ONE solve, ms to 
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); the batch axis is sharded, the solves are
 independent, and the only exchange is one all-gather of the per-problem cost per poll (pyddp.shard).
+
+A plain run sets up, warms up, times --steps sweeps and prints the headline line (`ms_per_step` = wall clock of one timed sweep).
+--dump-outputs DIR also writes what the timed sweeps left for a caller (pddp_store) as .npy files; the inputs are seeded, so two builds
+can be compared output for output.  --full adds every other figure: per-kernel times and roofline, side rows, latency, other
+configurations, the CPU baseline.
 """
 import argparse
 import json
@@ -31,6 +36,8 @@ import pyddp  # noqa: E402
 from pyddp import shard  # noqa: E402
 
 BENCH_BATCH = 16384       # independent problems per GPU of the headline line (tests/test_fp32_bar.py runs its what-the-bench-runs cases at this size)
+DUMP_SAMPLE = 256         # problems whose outputs --dump-outputs writes (KT of all 16384 alone is 822 MB) ...
+DUMP_BYTES = 64 << 20     # ... and at most this many bytes in all
 MFMA_F32_PEAK_TFLOPS = 157.3   # dense fp32 matrix-core peak of MI355X (256 CUs x 4 SIMDs x 64 flop/cycle x 2.4 GHz)
 HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E ~ 8 TB/s
 PHASES = ("bp", "fp", "ls", "nis")                      # the four phases of a sweep, in launch order (per-phase figures of the latency block)
@@ -233,7 +240,16 @@ def main():
                          "64 / N per GPU, exchanges through the C ABI's own RCCL collectives (pddp_comm_*)")
     ap.add_argument("--rows", action="store_true", help="only the rows beside the headline (other BASELINE configs, widening): for rocprofv3 passes over THEIR kernels "
                                                         "(tools/pmc_rows.sh); prints them as one JSON object, not the bench line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: accepted fraction and cost of the timed sweeps, per-kernel times and roofline, the lean_cost_to_go side row, "
+                         "time to convergence, single-problem latency, widening, other BASELINE configs, the bit-exact family and the CPU baseline "
+                         "(the --no-* options switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed sweeps, write what pddp_store returns for them (x, u, KT, Jout, alphaOut, dmax) to DIR/<name>.npy in float32 / float64, "
+                         "for a fixed seeded sample of the problems (rank 0's problems when --gpus > 1); the headline workload only")
     args = ap.parse_args()
+    if args.dump_outputs and (args.rows or args.workload != "config2"):
+        ap.error("--dump-outputs writes the outputs of the headline workload only")
     if args.rows:
         print(json.dumps({"other_baseline_configs": other_config_rows(0), "widening": widening_rows(0), "bit_exact_family": bit_exact_family_row(0)}))
         return
@@ -273,8 +289,45 @@ def main():
     t_local = time.perf_counter() - t0
     t = shard.max_over_ranks(ctx, t_local)
 
+    line = {"metric": "DDP iterations/sec (Kuka iiwa14 N=128, 8 alphas, 4 shooting segments)", "value": round(ctx.world * B * K / t, 1),
+            "unit": "DDP iterations/s", "n_gpus": ctx.world, "steps": K, "warmup": W, "ms_per_step": round(1e3 * t / K, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2]: Kuka iiwa14 RBD (n=14,m=7), N=128, 8 alphas x 4 shooting segments, Euler, fp32, "
+                                   "joint cost, T=0.5 s, WAFR example inputs + N(0,1e-3) velocity noise",
+                       "problems_per_gpu": B, "problems_total": ctx.world * B, "hipgraph": bool(args.graph), "sharding": "batch axis, no data-path collective",
+                       "cost_to_go_slots_written": "block boundaries only (pddp_config.boundary_cost_to_go_only)" if lean else "all", "handle_options": "lean" if lean else "library defaults"},
+            "rccl_ranks_seen": ctx.world if ctx.backend == "nccl" else (ctx.world if ctx.world == 1 else 0), "dist_backend": ctx.backend or "none"}
+    out = s.store() if (args.full or args.dump_outputs) else None     # what a caller of the timed path receives (pddp_store), before anything else runs on the handle
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    if args.full:
+        full_figures(line, ctx, args, torch, s, out, cfg, x0, u0, xg, t_local)
+    else:
+        s.close()
+    if ctx.rank == 0:
+        print(json.dumps(line), flush=True)
+    shard.finalize(ctx)
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: pddp_store's arrays after the timed sweeps, one .npy per array, for the problems of a fixed seeded sample (at most DUMP_SAMPLE, and at most
+    DUMP_BYTES in all); sample_problems.npy holds their indices.  Integer arrays are written as float32 (exact: step-size indices)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in out.items()}
+    B = len(arrays["x"])
+    per_problem = sum(v[0].nbytes for v in arrays.values())
+    pick = np.sort(np.random.default_rng(2024).choice(B, max(1, min(B, DUMP_SAMPLE, DUMP_BYTES // per_problem)), replace=False))
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v[pick])
+    np.save(os.path.join(path, "sample_problems.npy"), pick.astype(np.float64))
+
+
+def full_figures(line, ctx, args, torch, s, out, cfg, x0, u0, xg, t_local):
+    """--full: every figure beside the headline, added to `line`.  Closes the headline handle `s` (its outputs `out` were stored right after the timed sweeps)."""
+    K, W, B = args.steps, args.warmup, args.batch
+    N, M, A, n, m = 128, 4, 8, 14, 7
+    lean = 1 if args.lean_ctg else 0
     # ---- what happened in the timed sweeps (honesty: accepted / rejected iterations, decrease of J)
-    out = s.store()
     done, iters = s.status()
     acc = np.mean([(out["alphaOut"][b][W + 1: W + K + 1] >= 0).mean() for b in range(min(B, 64))])
     J_all = shard.allgather_costs(ctx, s.device_array("Jout"), B, cfg.max_iter + 2, int(iters.min()) - 1)   # RCCL exchange
@@ -319,21 +372,14 @@ def main():
                 sweep_traffic = float(sum(per))
     roof = roofline_record(dom_name, dom_ms, kern, alg_of, B, N, M, traffic, counters, tsrc, sweep_bytes, t_local / K, keep_ctg=not lean, per_kernel_traffic=per_kernel_traffic, A=A, n=n, m=m)
 
-    line = {"metric": "DDP iterations/sec (Kuka iiwa14 N=128, 8 alphas, 4 shooting segments)", "value": round(ctx.world * B * K / t, 1),
-            "unit": "DDP iterations/s", "n_gpus": ctx.world, "steps": K, "warmup": W, "ms_per_step": round(1e3 * t / K, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: Kuka iiwa14 RBD (n=14,m=7), N=128, 8 alphas x 4 shooting segments, Euler, fp32, "
-                                   "joint cost, T=0.5 s, WAFR example inputs + N(0,1e-3) velocity noise",
-                       "problems_per_gpu": B, "problems_total": ctx.world * B, "hipgraph": bool(args.graph), "sharding": "batch axis, no data-path collective",
-                       "cost_to_go_slots_written": "block boundaries only (pddp_config.boundary_cost_to_go_only)" if lean else "all", "handle_options": "lean" if lean else "library defaults"},
-            "rccl_ranks_seen": ctx.world if ctx.backend == "nccl" else (ctx.world if ctx.world == 1 else 0), "dist_backend": ctx.backend or "none",
+    line.update({
             "accepted_fraction_in_timed_sweeps": round(float(acc), 3),
             "J_first_last_mean": [round(float(J_all[:, 0].mean()), 3), round(float(J_all[:, -1].mean()), 3)],
             # top-level copies of the HBM figures (the north-star metric; nested keys do not survive every consumer of this line)
             "hbm_frac_of_peak_dominant_kernel": (roof.get("hbm") or {}).get("frac_of_peak"),
             "hbm_frac_of_peak_whole_sweep": None if sweep_traffic is None else round(sweep_traffic / (t_local / K) / 1e9 / HBM_PEAK_GBS, 4),
             "hbm_bytes_per_sweep": sweep_traffic, "hbm_traffic_source": tsrc,
-            "roofline": roof}
+            "roofline": roof})
 
     s.close()
     # ---- side row: the same sweeps on a handle with boundary_cost_to_go_only = 1 (interior cost-to-go slots not written: they are no output of runiLQR_GPU and no
@@ -382,9 +428,6 @@ def main():
         line["cpu_baseline"] = guarded(cpu_baseline)
     elif ctx.rank == 0:
         line["cpu_baseline"] = None
-    if ctx.rank == 0:
-        print(json.dumps(line), flush=True)
-    shard.finalize(ctx)
 
 
 def config3_sharded(args):

@@ -24,9 +24,9 @@ pytestmark = pytest.mark.skipif(not os.path.exists(mx_isa.HIPCC), reason="needs 
 
 
 @pytest.fixture(scope="module")
-def product_build():
+def product_build(tmp_path_factory):
     """ONE device compile of the product translation unit shared by the tests below: (assembly, resource remarks)"""
-    return mx_isa.compile_asm(out="/tmp/isa/test_mx.s")
+    return mx_isa.compile_asm(out=str(tmp_path_factory.mktemp("isa") / "test_mx.s"))
 
 
 @pytest.fixture(scope="module")
@@ -63,8 +63,8 @@ def test_no_scratch_and_six_waves_for_the_benched_instantiation(product_build):
             assert v["scratch"] == 0, (k, v)
 
 
-def test_a_fifth_gain_store_turns_the_check_red():
-    asm, _ = mx_isa.compile_asm(defs=["-DPDDP_MX_TEST_EXTRA_STORE=1"], out="/tmp/isa/test_mx_extra.s")
+def test_a_fifth_gain_store_turns_the_check_red(tmp_path):
+    asm, _ = mx_isa.compile_asm(defs=["-DPDDP_MX_TEST_EXTRA_STORE=1"], out=str(tmp_path / "test_mx_extra.s"))
     bodies = mx_isa.kernel_bodies(asm)
     flagged = 0
     for name, body in bodies.items():

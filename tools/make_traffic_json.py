@@ -30,7 +30,7 @@ try:
     build["git_dirty"] = bool(subprocess.check_output(["git", "-C", root, "status", "--porcelain", "--", "parallel-ddp_amd/csrc", "include", "parallel-ddp_amd/Makefile"], text=True).strip())
 except Exception:      # noqa: BLE001
     build["git_head"] = None
-out = {"batch": batch, "handle_options": handle_options, "build": build, "source": f"profiles/{sub} (tools/pmc_pass.sh: separate rocprofv3 --pmc passes of `python bench.py --no-cpu-baseline --no-latency --no-convergence --no-lean-row --steps 20`)", "kernels": {}}
+out = {"batch": batch, "handle_options": handle_options, "build": build, "source": f"profiles/{sub} (tools/pmc_pass.sh: separate rocprofv3 --pmc passes of `python bench.py --full --no-cpu-baseline --no-latency --no-convergence --no-lean-row --steps 20`)", "kernels": {}}
 lines = ["# Counter passes (rocprofv3 --pmc, kernel-trace only) of the bench sweep, per kernel, averages per launch", "",
          "| kernel | HBM read MB (2 x FETCH_SIZE) | HBM write MB | VALU instr / wave | MFMA instr / wave | VALU-active share of wave time | waiting on memory (s_waitcnt) | issue stalls | MFMA pipe busy share |",
          "|---|---|---|---|---|---|---|---|---|"]

@@ -2,7 +2,7 @@
 # One ad-hoc counter pass of the headline bench: usage tools/pmc_adhoc.sh <tag> "<counters>" [bench args].  Summary -> gpurun_out/pmc_<tag>/summary.txt
 TAG=$1; CTR=$2; shift; shift
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$ROOT/gpurun_out/pmc_$TAG; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-timeout 900 rocprofv3 --output-format csv --kernel-trace --pmc $CTR -d $OUT/a -o run -- python $ROOT/bench.py --no-cpu-baseline --no-latency --no-convergence --steps 10 "$@" > $OUT/a.log 2>&1
+timeout 900 rocprofv3 --output-format csv --kernel-trace --pmc $CTR -d $OUT/a -o run -- python $ROOT/bench.py --full --no-cpu-baseline --no-latency --no-convergence --steps 10 "$@" > $OUT/a.log 2>&1
 python - <<PY > $OUT/summary.txt
 import csv, collections, statistics, glob
 for f in sorted(glob.glob("$OUT/*/run_counter_collection.csv")):

@@ -4,7 +4,7 @@ TAG=$1; shift
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/qs_$TAG
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-timeout 600 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT -o run -- python $ROOT/bench.py --no-cpu-baseline --no-latency $* > $OUT/bench.log 2>&1
+timeout 600 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT -o run -- python $ROOT/bench.py --full --no-cpu-baseline --no-latency $* > $OUT/bench.log 2>&1
 python - <<PY
 import csv
 for r in csv.DictReader(open("$OUT/run_kernel_stats.csv")):
