@@ -182,6 +182,16 @@ int pddp_set_cost(pddp_handle h, double Q1, double Q2, double R, double QF1, dou
  * state) / substeps, sic (:137-138).  *failed = 1 when the time leaves the plan (k >= N-2): state untouched, error 0 (:129-130). */
 int pddp_simulate(pddp_handle h, const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps,
                   const void* goal_xyz, void* xActual_inout, double* avg_err, int* failed);
+/* pddp_simulate for every problem of the handle in one launch (one wavefront per problem, the same double-precision body: per problem the results are
+ * bit-identical to pddp_simulate's).  x [batch][N][n], u [batch][N][m], KT [batch][N][n*m] = host plans in the layout of pddp_store / pddp_mpc_solve; all
+ * three NULL: every problem follows the solution the handle holds on the device -- what pddp_store would return now; after pddp_mpc_solve that call's
+ * x, u, KT, the fall-back of a solve that took no step included -- and nothing is uploaded (a mixture of NULL and non-NULL is PDDP_EINVAL).
+ * t0_us [batch], elapsed_us [batch] (each >= 0), one `substeps` >= 1 for the batch; goal_xyz [batch][3] in the handle's dtype (arm only, may be NULL: no
+ * error metric); xActual_inout [batch][n]; avg_err [batch], failed [batch] (either may be NULL).  A problem whose time leaves its plan aborts alone
+ * (state untouched, error 0, failed 1).  Enqueued on the solver's stream behind whatever is there, synchronises once, and changes nothing that a later
+ * pddp_iterate / pddp_mpc_solve / pddp_store reads: the solution arrays are only read. */
+int pddp_simulate_batch(pddp_handle h, const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us, int substeps,
+                        const void* goal_xyz, void* xActual_inout, double* avg_err, int* failed);
 /* compute_eePos_scratch (plants/dynamics_arm.cuh:1953-1960): tool point (x, y, z, roll, pitch, yaw) of `count` states [count][n] -> [count][6]. */
 int pddp_ee_pos(pddp_handle h, int count, const void* x, void* eePos);
 /* The HIP stream every kernel of this handle is enqueued on (a hipStream_t). */

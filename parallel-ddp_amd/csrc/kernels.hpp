@@ -1007,6 +1007,19 @@ __global__ __launch_bounds__(64) void k_plant_sim(const void* model, PlantSimArg
     __shared__ PlantSimScratch<PD, T> s;
     plant_sim_body<PD, INTEG, T>(this_wave(), s, model, a);
 }
+// the same body for every problem of the handle: grid (batch), block 64 -- one wavefront per problem.  px / pu / pKT: the uploaded plans [batch][N][...], or all null:
+// every problem follows the solution the handle holds (what pddp_store copies out: mpc_store_body's addressing), which this kernel only reads
+template <typename PD, int INTEG, typename T>
+__global__ __launch_bounds__(64) void k_plant_sim_batch(const void* model, const PlantSimBatchIn<PD, T>* in, PlantSimBatchOut<PD, T>* out, const T* px, const T* pu,
+                                                        const T* pKT, Buffers<T> b, int N, double step_us, int substeps, int has_goal, double ee_z) {
+    constexpr int NX = PD::NX, NU = PD::NU;
+    __shared__ PlantSimScratch<PD, T> s;
+    const size_t pb = blockIdx.x;
+    const T* x = px ? px + pb * N * NX : b.xb + (pb * 2 + b.state[pb].cur) * N * NX;
+    const T* u = px ? pu + pb * N * NU : b.ucur + pb * N * NU;
+    const T* KT = px ? pKT + pb * N * NX * NU : b.KT + pb * N * NX * NU;
+    plant_sim_batch_body<PD, INTEG, T>(this_wave(), s, model, in[pb], out[pb], x, u, KT, N, step_us, substeps, has_goal != 0, ee_z);
+}
 // tool point of `count` states: grid (count), block 64
 template <typename P, typename T>
 __global__ __launch_bounds__(64) void k_ee_pos(const void* model, T ee_z, const T* x, T* out) {

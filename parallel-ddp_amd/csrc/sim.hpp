@@ -95,6 +95,33 @@ PDDP_HD void plant_sim_body(const Wave& w, PlantSimScratch<PD, T>& s, const void
     (void)NP;
 }
 
+// ---- the batched form (pddp_simulate_batch): one wavefront per problem of the handle, the body above unchanged.  What differs per problem does not travel as
+// kernel arguments but as one packed record each way: ONE transfer up for the batch, ONE transfer back.
+template <typename PD, typename T>
+struct PlantSimBatchIn {
+    double t0_us, elapsed_us;
+    T goal[3];                    // tool-point goal xyz (read only when the call carries goals)
+    T x[PD::NX];                  // measured state at t0 + 0
+};
+template <typename PD, typename T>
+struct PlantSimBatchOut {         // state | error | failed
+    T x[PD::NX];                  // state after elapsed_us (the measured state when the problem aborted)
+    double out[2];                // average tracking error, failed flag: what plant_sim_body writes through PlantSimArgs::out
+};
+
+// x / u / KT: THIS problem's plan, already resolved by the caller -- a slice of the uploaded plans, or the solution the handle holds (read only either way)
+template <typename PD, int INTEG, typename T>
+PDDP_HD void plant_sim_batch_body(const Wave& w, PlantSimScratch<PD, T>& s, const void* model, const PlantSimBatchIn<PD, T>& in, PlantSimBatchOut<PD, T>& out,
+                                  const T* x, const T* u, const T* KT, int N, double step_us, int substeps, bool has_goal, double ee_z) {
+    PDDP_FOR(i, PD::NX) out.x[i] = in.x[i];             // the body advances the state in place: an abort leaves this copy, i.e. the measured state
+    wsync(w);
+    PlantSimArgs<T> a;
+    a.x = x; a.u = u; a.KT = KT; a.N = N; a.step_us = step_us;
+    a.t0_us = in.t0_us; a.elapsed_us = in.elapsed_us; a.substeps = substeps; a.goal = has_goal ? in.goal : nullptr; a.ee_z = ee_z;
+    a.xActual = out.x; a.out = out.out;
+    plant_sim_body<PD, INTEG, T>(w, s, model, a);
+}
+
 // compute_eePos_scratch (plants/dynamics_arm.cuh:1953-1960): tool point (x, y, z, roll, pitch, yaw) of one state, arm only
 template <typename P, typename T>
 PDDP_HD void ee_pos_body(const Wave& w, typename P::Scratch& plant, EeScratch<T>& ee, T* xs, T* us, T* qdd, const void* model, T ee_z, const T* x, T* out) {

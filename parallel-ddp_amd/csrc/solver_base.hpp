@@ -47,6 +47,8 @@ struct SolverBase {
     virtual int iterate_traced(int sweeps, double* phase_ms, int first_sweep, int stride) = 0;
     virtual int simulate(const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps, const void* goal, void* xActual,
                          double* avg_err, int* failed) = 0;
+    virtual int simulate_batch(const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us, int substeps, const void* goal,
+                               void* xActual, double* avg_err, int* failed) = 0;
     virtual int ee_pos(int count, const void* x, void* out) = 0;
     virtual int set_cost(double Q1, double Q2, double R, double QF1, double QF2) = 0;
     virtual int set_cost_ee(const double* v) = 0;

@@ -166,6 +166,9 @@ struct Solver : SolverBase {
         if (graph_n) hipGraphExecDestroy(graph_n);
         for (void* p : allocs) hipFree(p);
         for (void* p : scratch_buf) if (p) hipFree(p);
+        if (d_simb) hipFree(d_simb);
+        if (d_simb_plan) hipFree(d_simb_plan);
+        if (h_simb) hipHostFree(h_simb);
         if (h_stage) hipHostFree(h_stage);
         if (h_state) hipHostFree(h_state);
         if (stream) hipStreamDestroy(stream);
@@ -912,6 +915,72 @@ struct Solver : SolverBase {
         HIPCHK(hipStreamSynchronize(stream));
         if (avg_err) *avg_err = ho[0];
         if (failed) *failed = (int)ho[1];
+        return 0;
+    }
+    // pddp_simulate_batch: the same body for every problem of the handle, one wavefront each (k_plant_sim_batch).  Its buffers are its own, grow-only and released with
+    // the handle -- not the helpers' scratch slots above, not the MPC call's staging: whatever else is enqueued on the stream keeps what it owns.  Per call: one transfer
+    // up (the packed per-problem records) + the three plans when they come from the host, one launch, one transfer back (state | error | failed), one synchronisation.
+    unsigned char* d_simb = nullptr; size_t d_simb_cap = 0;          // device: input records, then output records
+    T* d_simb_plan = nullptr; size_t d_simb_plan_cap = 0;            // device: uploaded plans x | u | KT
+    unsigned char* h_simb = nullptr; size_t h_simb_cap = 0;          // pinned: the same two record areas
+    int simulate_batch(const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us, int substeps, const void* goal, void* xActual,
+                       double* avg_err, int* failed) override {
+        using In = PlantSimBatchIn<PD, T>; using Out = PlantSimBatchOut<PD, T>;
+        const size_t B = cfg.batch, N = cfg.N;
+        if ((x != nullptr) != (u != nullptr) || (x != nullptr) != (KT != nullptr))
+            return fail(PDDP_EINVAL, "pddp_simulate_batch: x, u and KT are either all given (host plans) or all NULL (the solution the handle holds)");
+        if (substeps < 1) return fail(PDDP_EINVAL, "pddp_simulate_batch: substeps >= 1");
+        for (size_t i = 0; i < B; i++) if (!(elapsed_us[i] >= 0)) return fail(PDDP_EINVAL, "pddp_simulate_batch: elapsed_us[" + std::to_string(i) + "] must be >= 0");
+        if (!model_d) {
+            typename PD::Model hm; fill_model(hm, cfg);
+            HIPCHK(hipMalloc(&model_d, sizeof(hm))); allocs.push_back(model_d);
+            HIPCHK(hipMemcpy(model_d, &hm, sizeof(hm), hipMemcpyHostToDevice));
+        }
+        const size_t in_bytes = (B * sizeof(In) + 15) / 16 * 16, rec_bytes = in_bytes + B * sizeof(Out);
+        if (d_simb_cap < rec_bytes) {
+            HIPCHK(hipStreamSynchronize(stream));
+            if (d_simb) hipFree(d_simb);
+            if (h_simb) hipHostFree(h_simb);
+            d_simb = nullptr; h_simb = nullptr; d_simb_cap = 0; h_simb_cap = 0;
+            if (hipMalloc((void**)&d_simb, rec_bytes) != hipSuccess) return fail(PDDP_ENOMEM, "pddp_simulate_batch: hipMalloc failed for the per-problem records");
+            d_simb_cap = rec_bytes;
+            HIPCHK(hipHostMalloc((void**)&h_simb, rec_bytes, hipHostMallocDefault));
+            h_simb_cap = rec_bytes;
+        }
+        const size_t nx = B * N * NX, nu = B * N * NU, nk = B * N * NX * NU;
+        const T *px = nullptr, *pu = nullptr, *pKT = nullptr;
+        if (x) {
+            if (d_simb_plan_cap < nx + nu + nk) {
+                HIPCHK(hipStreamSynchronize(stream));
+                if (d_simb_plan) hipFree(d_simb_plan);
+                d_simb_plan = nullptr; d_simb_plan_cap = 0;
+                if (hipMalloc((void**)&d_simb_plan, (nx + nu + nk) * sizeof(T)) != hipSuccess) return fail(PDDP_ENOMEM, "pddp_simulate_batch: hipMalloc failed for the uploaded plans");
+                d_simb_plan_cap = nx + nu + nk;
+            }
+            px = d_simb_plan; pu = px + nx; pKT = pu + nu;
+            HIPCHK(hipMemcpyAsync(d_simb_plan, x, nx * sizeof(T), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_simb_plan + nx, u, nu * sizeof(T), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_simb_plan + nx + nu, KT, nk * sizeof(T), hipMemcpyHostToDevice, stream));
+        }
+        In* hin = reinterpret_cast<In*>(h_simb);
+        for (size_t i = 0; i < B; i++) {
+            In& r = hin[i];
+            r.t0_us = t0_us[i]; r.elapsed_us = elapsed_us[i];
+            for (int c = 0; c < 3; c++) r.goal[c] = goal ? ((const T*)goal)[3 * i + c] : T(0);
+            std::memcpy(r.x, (const T*)xActual + i * NX, NX * sizeof(T));
+        }
+        HIPCHK(hipMemcpyAsync(d_simb, h_simb, B * sizeof(In), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL((k_plant_sim_batch<PD, INTEG, T>), dim3((unsigned)B), dim3(64), 0, stream, (const void*)model_d, (const In*)d_simb, (Out*)(d_simb + in_bytes), px, pu, pKT, b,
+                           (int)N, cfg.total_time / (cfg.N - 1) * 1000.0 * 1000.0, substeps, goal ? 1 : 0, cfg.ee_on_link_z);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_simb + in_bytes, d_simb + in_bytes, B * sizeof(Out), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        const Out* hout = reinterpret_cast<const Out*>(h_simb + in_bytes);
+        for (size_t i = 0; i < B; i++) {
+            std::memcpy((T*)xActual + i * NX, hout[i].x, NX * sizeof(T));
+            if (avg_err) avg_err[i] = hout[i].out[0];
+            if (failed) failed[i] = (int)hout[i].out[1];
+        }
         return 0;
     }
     int ee_pos(int count, const void* x, void* out) override {

@@ -354,6 +354,25 @@ class Solver:
         self._chk(self.lib.pddp_simulate(self.h, _p(x), _p(u), _p(KT), float(t0_us), float(elapsed_us), int(substeps), _p(g), _p(xa), C.byref(err), C.byref(failed)))
         return xa, err.value, failed.value
 
+    def simulate_batch(self, t0_us, elapsed_us, substeps=150, goal_xyz=None, xActual=None, x=None, u=None, KT=None):
+        """pddp_simulate_batch: the simulated robot for every problem of the handle in one launch.  x / u / KT [B][N][...] = host plans; all three None: every
+        problem follows the solution the handle holds on the device (nothing is uploaded).  t0_us, elapsed_us broadcast to [B], goal_xyz to [B][3].
+        Returns (xActual [B][n] after elapsed_us, average tracking error [B], failed [B])."""
+        B = self.cfg.batch
+        if xActual is None:
+            raise PddpError("pddp_simulate_batch: xActual (the measured states [B][n]) is required")
+        plans = [None if a is None else self.arr(a) for a in (x, u, KT)]
+        for a, per in zip(plans, (self.n, self.m, self.n * self.m)):
+            assert a is None or a.size == B * self.cfg.N * per
+        xa = np.array(np.broadcast_to(self.arr(xActual), (B, self.n)), dtype=self.dtype, order="C")
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0_us, np.float64), (B,)))
+        el = np.ascontiguousarray(np.broadcast_to(np.asarray(elapsed_us, np.float64), (B,)))
+        g = None if goal_xyz is None else np.ascontiguousarray(np.broadcast_to(self.arr(goal_xyz), (B, 3)))
+        err, failed = np.zeros(B, np.float64), np.zeros(B, np.int32)
+        self.lib.pddp_simulate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_simulate_batch(self.h, _p(plans[0]), _p(plans[1]), _p(plans[2]), _p(t0), _p(el), int(substeps), _p(g), _p(xa), _p(err), _p(failed)))
+        return xa, err, failed
+
     def ee_pos(self, x):
         """pddp_ee_pos: tool point (x, y, z, roll, pitch, yaw) of states [count][n]."""
         x = self.arr(x).reshape(-1, self.n)
