@@ -14,8 +14,7 @@
 #include "bp.hpp"
 #include "fp.hpp"
 #include "nis.hpp"
-#include "solver_state.hpp"
-#include "iiwa14_model_data.h"
+#include "handle_setup.hpp"
 
 using namespace pddp;
 
@@ -37,17 +36,6 @@ extern "C" int pddp_cpu_thread_counts(int M, int cores, int* bp, int* fsim, int*
 
 namespace {
 
-template <typename T> void fill_model(ArmModel<T>& m, const pddp_config& c) {
-    const int v = c.wafr_urdf ? 1 : 0;
-    for (int b = 0; b < 7; b++) {
-        for (int i = 0; i < 36; i++) m.I[36 * b + i] = (T)IIWA14_SPATIAL_INERTIA[v][b][i];
-        for (int i = 0; i < 16; i++) m.F[16 * b + i] = (T)IIWA14_JOINT_FRAME[v][b][i];
-    }
-    m.grav = (T)(c.mpc_mode ? 0.0 : 9.81);                  // plants/dynamics_arm.cuh:42-46
-    arm_model_apply_ee_type(m, c.wafr_urdf, c.ee_type);
-}
-void fill_model(EmptyModel& m, const pddp_config&) { m.unused = 0; }
-
 // threads of one phase: the reference creates them per phase and joins them (e.g. fpHelpers.cuh:425-441)
 struct Phase {
     std::vector<std::thread> th;
@@ -64,9 +52,11 @@ int run_cpu(const pddp_config& c, const pddp_cpu_buffers& B, T* x0, T* u0, const
     constexpr int NX = P::NX, NU = P::NU, NM = NX + NU;
     const int N = c.N, M = c.M, A = c.A;
     Dims dm; dm.N = N; dm.M = M; dm.A = A; dm.NB = N / M;
-    CostWeights<T> cw{}; cw.Q1 = (T)c.Q1; cw.Q2 = (T)c.Q2; cw.R = (T)c.R; cw.QF1 = (T)c.QF1; cw.QF2 = (T)c.QF2; cw.ee = 0; cw.limits = c.use_limits;
-    cw.fd_eps = c.use_finite_diff ? c.finite_diff_epsilon : 0.0;      // USE_FINITE_DIFF: integratorGradientThreaded's other definition (nisInitHelpers.cuh:185-201)
-    const T dt = (T)(c.total_time / (N - 1));                // TIME_STEP, config.cuh:136
+    CostWeights<T> cw = cost_weights_of<T, P::PLANT>(c);     // (fd_eps: USE_FINITE_DIFF is integratorGradientThreaded's other definition, nisInitHelpers.cuh:185-201)
+    cw.ee = 0;                                               // joint-space cost only (EE_COST 0): the entry points refuse ee_cost
+    cw.limits = c.use_limits;                                // USE_LIMITS_FLAG as the caller set it, whatever the plant (only the arm's derivatives read it)
+    cw.smooth_abs = 0; cw.sa = 0; cw.sa2 = 0;                // no smooth-abs: it belongs to the end-effector cost
+    const T dt = time_step<T>(c);
     typename P::Model model; fill_model(model, c);
 #ifdef PDDP_REF_PLANT_FILE
     if constexpr (P::PLANT == 5) { const std::string complaint = ref_plugin_setup<T>(N); if (!complaint.empty()) return cpu_fail(PDDP_EINVAL, complaint); }

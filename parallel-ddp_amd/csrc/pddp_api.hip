@@ -1,5 +1,6 @@
 // libpddp.so: host side of the C ABI declared in include/pddp.h.  gfx950 only; no CPU fallback.
 #include "solver_base.hpp"
+#include "handle_setup.hpp"
 
 static thread_local std::string g_err;
 extern "C" const char* pddp_last_error(void) { return g_err.c_str(); }
@@ -13,31 +14,12 @@ static constexpr int kMaxPlant = 4;
 static int user_nx() { return -1; }
 static int user_nu() { return -1; }
 #endif
-extern "C" int pddp_state_size(int plant) { return plant == 1 ? 2 : plant == 2 ? 4 : plant == 3 ? 12 : plant == 4 ? 14 : plant == 5 ? user_nx() : -1; }
-extern "C" int pddp_control_size(int plant) { return plant == 1 ? 1 : plant == 2 ? 1 : plant == 3 ? 4 : plant == 4 ? 7 : plant == 5 ? user_nu() : -1; }
+extern "C" int pddp_state_size(int plant) { return plant == 5 ? user_nx() : pddp::builtin_state_size(plant); }
+extern "C" int pddp_control_size(int plant) { return plant == 5 ? user_nu() : pddp::builtin_control_size(plant); }
 
-// Reference defaults: config.cuh:24-61 per plant, :78-136 algorithm, plants/cost_arm.cuh:97-103 weights.
 extern "C" int pddp_default_config(pddp_config* c, int plant) {
     if (!c || plant < 1 || plant > kMaxPlant) return fail(PDDP_EINVAL, "plant must be 1..4 (5: the user plant of a `make user PLANT_POLICY=...` build)");
-    std::memset(c, 0, sizeof(*c));
-    c->plant = plant; c->dtype = 0;
-    c->N = plant == 4 ? 64 : 128; c->M = 4;                      // plant 5 (a user plant) starts from the pendulum's defaults
-    c->A = (plant == 3 || plant == 4) ? 16 : 32;
-    c->integrator = plant == 4 ? 1 : 3;
-    c->batch = 1; c->max_iter = 100; c->ignore_max_rho_exit = 1;
-    c->total_time = plant == 4 ? 0.5 : 4.0;
-    c->alpha_base = (plant == 3 || plant == 4) ? 0.5 : 0.75;
-    c->rho_init = plant == 4 ? 12.5 : (plant == 3 ? 1.0 : 10.0);
-    c->max_defect = plant == 2 ? 0.75 : 1.0;
-    c->tol_cost = 0.0001; c->exp_red_min = 0.05; c->exp_red_max = 1.25;
-    c->Q1 = 0.1; c->Q2 = 0.001; c->R = 0.0001; c->QF1 = 1000.0; c->QF2 = 1000.0;
-    c->Q_EE1 = 0.1; c->Q_EE2 = 0.0; c->QF_EE1 = 1000.0; c->QF_EE2 = 0.0; c->R_EE = 0.0001; c->Q_xEE = 0.0; c->QF_xEE = 0.0; c->Q_xdEE = 0.1; c->QF_xdEE = 1000.0;
-    c->ee_on_link_z = 0.0635;   // plants/cost_arm.cuh:104-115, dynamics_arm.cuh:57-58 (EE_TYPE 1)
-    c->use_finite_diff = 0; c->finite_diff_epsilon = 0.00001;   // config.cuh:68-71
-    c->use_limits = 0;                                          // config.cuh:171-173
-    c->use_smooth_abs = 0; c->smooth_abs_alpha = 0.2;           // config.cuh:174-176, cost_arm.cuh:116-118
-    c->ee_type = 1;                                             // dynamics_arm.cuh:50-52
-    std::memset(&c->kernels, 0, sizeof(c->kernels));           // the library's own kernel selection
+    pddp::default_config(c, plant);
     return 0;
 }
 
@@ -63,16 +45,8 @@ __global__ __launch_bounds__(256) void k_hbm_calib_dword(const float* __restrict
 extern "C" int pddp_create(const pddp_config* cfg, pddp_handle* out) {
     if (!cfg || !out) return fail(PDDP_EINVAL, "null argument");
     const pddp_config& c = *cfg;
-    if (c.plant < 1 || c.plant > kMaxPlant) return fail(PDDP_EINVAL, "plant must be 1..4 (5: the user plant of a `make user PLANT_POLICY=...` build)");
-    if (c.N < 4 || (c.N & (c.N - 1)) || c.N > 1024) return fail(PDDP_EINVAL, "N must be a power of two in [4,1024] (the reference's tree reductions assume it)");
-    if (c.M < 1 || c.N % c.M || c.N / c.M < 2 || c.M > 16) return fail(PDDP_EINVAL, "M must divide N, N/M >= 2, M <= 16");
-    if (c.A < 1 || c.A > 64 || c.batch < 1 || c.max_iter < 1) return fail(PDDP_EINVAL, "A in [1,64], batch >= 1, max_iter >= 1");
-    if (c.ee_cost && c.plant != 4) return fail(PDDP_EINVAL, "ee_cost: the end-effector cost family belongs to the KUKA arm (plant 4)");
-    if (c.ee_type < 0 || c.ee_type > 2) return fail(PDDP_EINVAL, "ee_type: EE_TYPE is 0 (no end effector), 1 (flange) or 2 (flange + peg) (dynamics_arm.cuh:50-65)");
-    if (c.use_limits && c.plant != 4) return fail(PDDP_EINVAL, "use_limits: USE_LIMITS_FLAG belongs to the KUKA arm's cost files (plant 4)");
-    if (c.use_smooth_abs && !(c.plant == 4 && c.ee_cost && c.smooth_abs_alpha > 0.0)) return fail(PDDP_EINVAL, "use_smooth_abs: USE_SMOOTH_ABS belongs to the end-effector cost (plant 4, ee_cost = 1, smooth_abs_alpha > 0)");
-    if (c.use_finite_diff && (c.integrator != 1 || c.ee_cost || !(c.finite_diff_epsilon > 0.0)))
-        return fail(PDDP_EINVAL, "use_finite_diff: the finite-difference [A B] is the Euler rule's (finiteDiffInner, nisInitHelpers.cuh:138-166), with the joint-space cost and a positive finite_diff_epsilon");
+    if (const char* complaint = pddp::config_complaint(c, kMaxPlant); complaint[0]) return fail(PDDP_EINVAL, complaint);
+    // the arm's lane-group kernels: 128 rollouts per workgroup, 32-bit element offsets
     if (c.plant == 4 && ((c.A > 8 && c.A % 8 == 0) ? 8 : c.A) * c.M > 128)
         return fail(PDDP_EINVAL, "KUKA arm: (candidates per workgroup) * M must not exceed 128 -- a workgroup rolls out 8 candidates when A is a multiple of 8, otherwise all A");
     if (c.plant == 4 && (double)c.batch * c.N * (c.A * 14 > 441 ? c.A * 14 : 441) >= 4294967296.0)

@@ -2,8 +2,8 @@
 // per-plant translation units only (pddp_plant_*.hip); the C ABI sees SolverBase (solver_base.hpp).
 #pragma once
 #include "solver_base.hpp"
-#include "iiwa14_model_data.h"
 #include "kernels.hpp"
+#include "handle_setup.hpp"
 #include "tl_launch.hpp"
 #include "mx_launch.hpp"
 
@@ -23,16 +23,6 @@ static const char* ksel_cf(const pddp_config& c) { return ksel(c.kernels.cf, {"t
 static const char* ksel_cf_bp(const pddp_config& c) { return ksel(c.kernels.cf_bp, {"ts", "coop", "gl", "gl32", "cl", "mq"}); }
 static const char* ksel_cf_fp(const pddp_config& c) { return ksel(c.kernels.cf_fp, {"ts", "coop", "cf"}); }
 static const char* ksel_cf_nis(const pddp_config& c) { return ksel(c.kernels.cf_nis, {"ts", "coop", "gl", "gl8", "kb16", "kb32", "kb64", "kb20"}); }
-template <typename T> static void fill_model(ArmModel<T>& m, const pddp_config& c) {
-    const int v = c.wafr_urdf ? 1 : 0;
-    for (int b = 0; b < 7; b++) {
-        for (int i = 0; i < 36; i++) m.I[36 * b + i] = (T)IIWA14_SPATIAL_INERTIA[v][b][i];
-        for (int i = 0; i < 16; i++) m.F[16 * b + i] = (T)IIWA14_JOINT_FRAME[v][b][i];
-    }
-    m.grav = (T)(c.mpc_mode ? 0.0 : 9.81);   // plants/dynamics_arm.cuh:42-46
-    arm_model_apply_ee_type(m, c.wafr_urdf, c.ee_type);
-}
-static void fill_model(EmptyModel& m, const pddp_config&) { m.unused = 0; }
 
 template <typename P, int INTEG, typename T>
 struct Solver : SolverBase {
@@ -164,6 +154,7 @@ struct Solver : SolverBase {
     ~Solver() override {
         if (graph) hipGraphExecDestroy(graph);
         if (graph_n) hipGraphExecDestroy(graph_n);
+        for (hipEvent_t e : trace_ev) hipEventDestroy(e);
         for (void* p : allocs) hipFree(p);
         for (void* p : scratch_buf) if (p) hipFree(p);
         if (d_simb) hipFree(d_simb);
@@ -252,37 +243,16 @@ struct Solver : SolverBase {
         // whose operation order is the reference's)
         if (const char* v = ksel_bp(cfg)) { bp_lane_groups = (std::string(v) == "lg"); bp_wide = (std::string(v) == "wide"); bp_mfma = (P::PLANT == 4 && std::string(v) == "mx"); }
         sweep_fused = bp_mfma && c.M > 1 && (!ksel_sweep(cfg) || std::string(ksel_sweep(cfg)) == "maps");
-        sp.max_iter = c.max_iter; sp.out_stride = c.max_iter + 2; sp.ignore_max_rho_exit = c.ignore_max_rho_exit; sp.tol_cost = c.tol_cost;
-        sp.exp_red_min = c.exp_red_min; sp.exp_red_max = c.exp_red_max; sp.max_defect = c.max_defect; sp.rho_init = c.rho_init; sp.ee_initial_cost_fix = c.ee_initial_cost_fix;
-        cw.Q1 = (T)c.Q1; cw.Q2 = (T)c.Q2; cw.R = (T)c.R; cw.QF1 = (T)c.QF1; cw.QF2 = (T)c.QF2;
-        cw.ee = c.ee_cost; cw.Q_EE1 = (T)c.Q_EE1; cw.Q_EE2 = (T)c.Q_EE2; cw.QF_EE1 = (T)c.QF_EE1; cw.QF_EE2 = (T)c.QF_EE2; cw.R_EE = (T)c.R_EE;
-        cw.Q_xEE = (T)c.Q_xEE; cw.QF_xEE = (T)c.QF_xEE; cw.Q_xdEE = (T)c.Q_xdEE; cw.QF_xdEE = (T)c.QF_xdEE; cw.ee_z = (T)c.ee_on_link_z;
-        cw.fd_eps = c.use_finite_diff ? c.finite_diff_epsilon : 0.0;
-        cw.limits = (P::PLANT == 4) ? c.use_limits : 0;
-        cw.smooth_abs = (P::PLANT == 4 && c.ee_cost) ? c.use_smooth_abs : 0; cw.sa = (T)c.smooth_abs_alpha; cw.sa2 = (T)(c.smooth_abs_alpha * c.smooth_abs_alpha);
-        dt = (T)(c.total_time / (c.N - 1));                       // TIME_STEP, config.cuh:136
+        sp = solver_params_of(c); cw = cost_weights_of<T, P::PLANT>(c); dt = time_step<T>(c);
         const size_t B = c.batch, N = c.N, A = c.A, M = c.M;
-        int rc = 0;
-#define AL(name, count) if ((rc = alloc(#name, &b.name, (count)))) return rc
-        AL(xs, B * A * N * NX); AL(us, B * A * N * NU); AL(ds, B * A * N * NX);
-        AL(xb, B * 2 * N * NX); AL(ucur, B * N * NU); AL(dcur, B * N * NX);
-        AL(P, 2 * B * N * NX * NX); AL(p, 2 * B * N * NX);     // double buffers: the second half is Pp / pp
-        AL(AB, B * N * NX * NM); AL(H, B * N * NM * NM); AL(g, B * N * NM);
-        AL(KT, B * N * NX * NU); AL(du, B * N * NU); AL(ApBK, B * N * NX * NX); AL(Bdu, B * N * NX);
-        AL(J, B * A); AL(dmax, B * A); AL(dJexp, B * 2 * M); AL(alpha, A); AL(xGoal, B * NX);
-        AL(Jout, B * (c.max_iter + 2)); AL(err, B * M); AL(alphaOut, B * (c.max_iter + 2)); AL(state, B);
-#undef AL
-        b.Pp = b.P + B * N * NX * NX; b.pp = b.p + B * N * NX;
-        arrays["P"].second /= 2; arrays["p"].second /= 2;
-        arrays["Pp"] = {b.Pp, arrays["P"].second}; arrays["pp"] = {b.pp, arrays["p"].second};
-        if ((rc = alloc("x_old", &mb.x_old, B * N * NX)) || (rc = alloc("u_old", &mb.u_old, B * N * NU)) || (rc = alloc("KT_old", &mb.KT_old, B * N * NX * NU))) return rc;
+        int rc = for_each_array<NX, NU>(c, b, mb, arrays, [this](const char* name, auto** out, size_t count) { return alloc(name, out, count); });
+        if (rc) return rc;
         // MPC inputs of a control cycle in ONE device run (one transfer): measured states | goals | shifts
         if ((rc = alloc("mpc_in", &d_xActual, 2 * B * NX + B * sizeof(int) / sizeof(T) + 2))) return rc;
         d_goal_in = d_xActual + B * NX; d_shift = reinterpret_cast<int*>(d_goal_in + B * NX);
         arrays["xActual"] = {d_xActual, B * NX * sizeof(T)}; arrays["shift"] = {d_shift, B * sizeof(int)};      // the views the facade's GPUVars name (MPCHelpers.hpp)
-        if ((rc = alloc("xTarget", &b.xTarget, B * NX)) || (rc = alloc("costk", &b.costk, B * N)) || (rc = alloc("tshift", &b.tshift, B))) return rc;
         std::vector<T> al(A);
-        for (size_t i = 0; i < A; i++) al[i] = (T)std::pow(c.alpha_base, (double)i);   // nisInitHelpers.cuh:829
+        alpha_table(c, al.data());
         HIPCHK(hipMemcpy(b.alpha, al.data(), A * sizeof(T), hipMemcpyHostToDevice));
         typename P::Model hm; fill_model(hm, c);
         void* dmodel = nullptr;
@@ -304,7 +274,6 @@ struct Solver : SolverBase {
                 if (c.ee_cost) { if ((rc = alloc("Hc", &b.Hc, B * N * 49 + 16))) return rc; }
             }
         }
-        if ((rc = alloc("Jpart", &b.Jpart, B * A * M)) || (rc = alloc("dpart", &b.dpart, B * A * M)) || (rc = alloc("parts_fresh", &b.parts_fresh, B))) return rc;
         // device tables of per-alpha pointers, the reference's d_x / d_u / d_d (nisInitHelpers.cuh:777-789,808-813)
         void** tab[3]; const char* tn[3] = {"xs_ptrs", "us_ptrs", "ds_ptrs"};
         T* base[3] = {b.xs, b.us, b.ds}; const size_t per[3] = {N * NX, N * NU, N * NX};
@@ -361,12 +330,19 @@ struct Solver : SolverBase {
             launch_fp(stream, 1);
             hipLaunchKernelGGL((k_adopt_slot0<P, T>), dim3(N, B), dim3(64), 0, stream, b, dm);
         }
-        hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), stream, b, dm, cw, sp, ignore_first_defect, rollout, ee, 0);
-        launch_nis(stream, 1);
-        if (ee) hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), stream, b, dm, cw, sp, ignore_first_defect, rollout, 2, 0);
+        launch_init_cost_and_setup(stream, ignore_first_defect, rollout, 0);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
+    }
+    // what starts a solve from the loaded trajectory: initial cost, setup kernel in init mode and, for the end-effector cost, the cost's second pass (its initial cost comes
+    // out of the setup kernel).  keep_alpha: the MPC call keeps alphaIndex (runiLQR_MPC_GPU does not reset it)
+    void launch_init_cost_and_setup(hipStream_t s, int ignore_first_defect, int rollout, int keep_alpha) {
+        const unsigned B = cfg.batch; const size_t N = cfg.N;
+        const int ee = cfg.ee_cost ? 1 : 0;
+        hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), s, b, dm, cw, sp, ignore_first_defect, rollout, ee, keep_alpha);
+        launch_nis(s, 1);
+        if (ee) hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), s, b, dm, cw, sp, ignore_first_defect, rollout, 2, keep_alpha);
     }
     // forward pass: the arm runs on lane groups (fp_lg.hpp), the closed-form plants on the wave-cooperative kernel
     // part: -1 everything; 0 only the linear sweep kernel (when the path has a separate one); 1 only the rollout kernel (per-kernel timing; kernels that sweep
@@ -544,8 +520,8 @@ struct Solver : SolverBase {
         static const int phase_of[6] = {PDDP_PHASE_BP, PDDP_PHASE_FP, PDDP_PHASE_FP, PDDP_PHASE_LS, PDDP_PHASE_NIS, PDDP_PHASE_NIS};
         const int part_of[6] = {-1, 0, maps_in_rollouts() ? -1 : 1, -1, 0, 1};      // (a rollout kernel that begins with the sweep is timed as it runs in production)
         HIPCHK(hipStreamSynchronize(stream));
-        const size_t need = 7 * (size_t)sweeps;
-        while (trace_ev.size() < need) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); trace_ev.push_back(e); }
+        note_sweeps_enqueued();
+        if (int erc = need_events(7 * (size_t)sweeps)) return erc;
         for (int i = 0; i < sweeps; i++) {
             HIPCHK(hipEventRecord(trace_ev[7 * i], stream));
             for (int k = 0; k < 6; k++) { if (nm[k][0]) launch_sweep(stream, phase_of[k], 0, part_of[k]); HIPCHK(hipEventRecord(trace_ev[7 * i + k + 1], stream)); }
@@ -579,10 +555,14 @@ struct Solver : SolverBase {
         HIPCHK(hipGraphDestroy(gr));
         return 0;
     }
+    // production sweeps leave the reference-layout views behind (marked here, not only in launch_fp: a hipGraph REPLAY does not pass through the launch functions)
+    void note_sweeps_enqueued() {
+        if (sweep_fused || mq_fused) fs_vars_stale = true;
+        if (cf_fp && cf_fp_staged) cand_stale = true;
+    }
     int iterate(int sweeps) override {
         if (bp_mfma && !keep_all_ctg()) lean_ctg_ran = true;
-        if ((sweep_fused || mq_fused) && sweeps > 0) fs_vars_stale = true;
-        if (cf_fp && cf_fp_staged && sweeps > 0) cand_stale = true;      // (here, not only in launch_fp: a hipGraph REPLAY runs the rollouts without passing through the launch function)
+        if (sweeps > 0) note_sweeps_enqueued();
         if (cfg.use_graph) {
             if (!graph || graph_mode != bench_mode + 2 * sp.max_iter) {
                 if (graph) { hipGraphExecDestroy(graph); graph = nullptr; }
@@ -606,12 +586,11 @@ struct Solver : SolverBase {
     // `sweeps` sweeps, kernel by kernel, an event after every launch; phase_ms[ph*stride + first_sweep + i] = duration of phase ph of sweep i, FIVE rows:
     // 0 backward pass, 1 forward pass (linear sweep + rollouts), 2 line search, 3 next-iteration setup, 4 the linear forward sweep's own kernel alone (a part of row 1:
     // the reference's sweepTime[], DDPWrappers.cuh:77; 0 on paths whose rollout kernel sweeps itself)
-    std::vector<hipEvent_t> trace_ev;
+    std::vector<hipEvent_t> trace_ev;             // grow-only, released with the handle
+    int need_events(size_t n) { while (trace_ev.size() < n) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); trace_ev.push_back(e); } return 0; }
     int iterate_traced(int sweeps, double* phase_ms, int first_sweep, int stride) override {
-        const size_t need = 6 * (size_t)sweeps;
-        if ((sweep_fused || mq_fused) && sweeps > 0) fs_vars_stale = true;
-        if (cf_fp && cf_fp_staged && sweeps > 0) cand_stale = true;
-        while (trace_ev.size() < need) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); trace_ev.push_back(e); }
+        if (sweeps > 0) note_sweeps_enqueued();
+        if (int erc = need_events(6 * (size_t)sweeps)) return erc;
         static const int phase_of[5] = {PDDP_PHASE_BP, PDDP_PHASE_FP, PDDP_PHASE_FP, PDDP_PHASE_LS, PDDP_PHASE_NIS};
         const bool own_sweep = !maps_in_rollouts();                                  // (otherwise the rollout kernel begins with it: row 4 stays 0)
         const int part_of[5] = {-1, 0, own_sweep ? 1 : -1, -1, -1};
@@ -637,7 +616,7 @@ struct Solver : SolverBase {
     int set_cost(double Q1, double Q2, double R, double QF1, double QF2) override {
         HIPCHK(hipStreamSynchronize(stream));
         cfg.Q1 = Q1; cfg.Q2 = Q2; cfg.R = R; cfg.QF1 = QF1; cfg.QF2 = QF2;
-        cw.Q1 = (T)Q1; cw.Q2 = (T)Q2; cw.R = (T)R; cw.QF1 = (T)QF1; cw.QF2 = (T)QF2;
+        cw = cost_weights_of<T, P::PLANT>(cfg);
         if (graph) { hipGraphExecDestroy(graph); graph = nullptr; graph_mode = -1; }   // the weights are kernel arguments baked into the captured sweep
         return 0;
     }
@@ -645,8 +624,7 @@ struct Solver : SolverBase {
         if (!cfg.ee_cost) return fail(PDDP_EINVAL, "pddp_set_cost_ee: the handle was not created with ee_cost = 1");
         HIPCHK(hipStreamSynchronize(stream));
         cfg.Q_EE1 = v[0]; cfg.Q_EE2 = v[1]; cfg.QF_EE1 = v[2]; cfg.QF_EE2 = v[3]; cfg.R_EE = v[4]; cfg.Q_xEE = v[5]; cfg.QF_xEE = v[6]; cfg.Q_xdEE = v[7]; cfg.QF_xdEE = v[8];
-        cw.Q_EE1 = (T)v[0]; cw.Q_EE2 = (T)v[1]; cw.QF_EE1 = (T)v[2]; cw.QF_EE2 = (T)v[3]; cw.R_EE = (T)v[4]; cw.Q_xEE = (T)v[5]; cw.QF_xEE = (T)v[6];
-        cw.Q_xdEE = (T)v[7]; cw.QF_xdEE = (T)v[8];
+        cw = cost_weights_of<T, P::PLANT>(cfg);
         drop_graph();
         return 0;
     }
@@ -691,10 +669,7 @@ struct Solver : SolverBase {
         if (!split_roll) hipLaunchKernelGGL((k_mpc_load<P, INTEG, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
         const int saved_max_iter = sp.max_iter;
         sp.max_iter = max_iter;                                  // acceptRejectTrajGPU(..., max_iter)
-        const int ee = cfg.ee_cost ? 1 : 0;
-        hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), stream, b, dm, cw, sp, ifd, 0, ee, 1);   // keeps alphaIndex (runiLQR_MPC_GPU does not reset it)
-        launch_nis(stream, 1);
-        if (ee) hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), stream, b, dm, cw, sp, ifd, 0, 2, 1);
+        launch_init_cost_and_setup(stream, ifd, 0, 1);
         HIPCHK(hipGetLastError());
         std::vector<int> done(B);
         int rc = 0;
@@ -785,15 +760,13 @@ struct Solver : SolverBase {
     int time_sweeps(int sweeps, float* ms_total, float* ms_phase) override {
         HIPCHK(hipStreamSynchronize(stream));
         if (!ms_phase) {                       // total only: the sweeps exactly as pddp_iterate enqueues them (graph replay if configured)
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-            HIPCHK(hipEventRecord(e0, stream));
-            int rc = iterate(sweeps);
+            int rc = need_events(2);                       // (the handle's own events: nothing to release on an error return)
             if (rc) return rc;
-            HIPCHK(hipEventRecord(e1, stream));
-            HIPCHK(hipEventSynchronize(e1));
-            if (ms_total) HIPCHK(hipEventElapsedTime(ms_total, e0, e1));
-            hipEventDestroy(e0); hipEventDestroy(e1);
+            HIPCHK(hipEventRecord(trace_ev[0], stream));
+            if ((rc = iterate(sweeps))) return rc;
+            HIPCHK(hipEventRecord(trace_ev[1], stream));
+            HIPCHK(hipEventSynchronize(trace_ev[1]));
+            if (ms_total) HIPCHK(hipEventElapsedTime(ms_total, trace_ev[0], trace_ev[1]));
             return 0;
         }
         // per phase: ONE pass, kernel by kernel, an event after every launch (the sweeps are not replayed a second time:
@@ -816,20 +789,12 @@ struct Solver : SolverBase {
         std::vector<SolverState<T>> st(cfg.batch);
         HIPCHK(hipStreamSynchronize(stream));        // the solver stream is non-blocking: order the copy after every enqueued sweep
         HIPCHK(hipMemcpy(st.data(), b.state, cfg.batch * sizeof(SolverState<T>), hipMemcpyDeviceToHost));
-        for (int i = 0; i < cfg.batch; i++) {
-            const auto& s = st[i]; pddp_state& o = out[i];
-            o.rho = s.rho; o.drho = s.drho; o.prevJ = s.prevJ; o.dJ = s.dJ; o.z = s.z; o.iter = s.iter; o.alphaIndex = s.alphaIndex;
-            o.ignore_defect = s.ignore_defect; o.accepted = s.accepted; o.done = s.done; o.cur = s.cur; o.cur2 = s.cur2; o.bp_retries = s.bp_retries; o.pw = s.pw;
-        }
+        for (int i = 0; i < cfg.batch; i++) to_public(st[i], out[i]);
         return 0;
     }
     int set_state(const pddp_state* in) override {
         std::vector<SolverState<T>> st(cfg.batch);
-        for (int i = 0; i < cfg.batch; i++) {
-            auto& s = st[i]; const pddp_state& o = in[i];
-            s.rho = (T)o.rho; s.drho = (T)o.drho; s.prevJ = (T)o.prevJ; s.dJ = (T)o.dJ; s.z = (T)o.z; s.iter = o.iter; s.alphaIndex = o.alphaIndex;
-            s.ignore_defect = o.ignore_defect; s.accepted = o.accepted; s.done = o.done; s.cur = o.cur; s.cur2 = o.cur2; s.bp_retries = o.bp_retries; s.took_step = 0; s.pw = o.pw; s.win_pending = (o.accepted == 1) ? 1 : 0;
-        }
+        for (int i = 0; i < cfg.batch; i++) from_public(in[i], st[i]);
         HIPCHK(hipStreamSynchronize(stream));
         HIPCHK(hipMemcpy(b.state, st.data(), cfg.batch * sizeof(SolverState<T>), hipMemcpyHostToDevice));
         return 0;
@@ -885,15 +850,18 @@ struct Solver : SolverBase {
     // ---- lock-step experiment helpers
     using PD = typename P::template Rebind<double>;
     void* model_d = nullptr;                           // the plant's constants in double (the simulated robot runs in double)
+    int ensure_model_d() {
+        if (model_d) return 0;
+        typename PD::Model hm; fill_model(hm, cfg);
+        HIPCHK(hipMalloc(&model_d, sizeof(hm))); allocs.push_back(model_d);
+        HIPCHK(hipMemcpy(model_d, &hm, sizeof(hm), hipMemcpyHostToDevice));
+        return 0;
+    }
     int simulate(const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps, const void* goal, void* xActual,
                  double* avg_err, int* failed) override {
         if (substeps < 1 || !(elapsed_us >= 0)) return fail(PDDP_EINVAL, "pddp_simulate: substeps >= 1 and elapsed_us >= 0");
         const size_t N = cfg.N;
-        if (!model_d) {
-            typename PD::Model hm; fill_model(hm, cfg);
-            HIPCHK(hipMalloc(&model_d, sizeof(hm))); allocs.push_back(model_d);
-            HIPCHK(hipMemcpy(model_d, &hm, sizeof(hm), hipMemcpyHostToDevice));
-        }
+        if (int mrc = ensure_model_d()) return mrc;
         const size_t nx = N * NX, nu = N * NU, nk = N * NX * NU;
         T* buf = nullptr; double* dout = nullptr;
         int rc;
@@ -904,7 +872,7 @@ struct Solver : SolverBase {
         HIPCHK(hipMemcpyAsync(buf + nx + nu + nk, xActual, NX * sizeof(T), hipMemcpyHostToDevice, stream));
         if (goal) HIPCHK(hipMemcpyAsync(buf + nx + nu + nk + NX, goal, 3 * sizeof(T), hipMemcpyHostToDevice, stream));
         PlantSimArgs<T> a;
-        a.x = buf; a.u = buf + nx; a.KT = buf + nx + nu; a.N = cfg.N; a.step_us = cfg.total_time / (cfg.N - 1) * 1000.0 * 1000.0;
+        a.x = buf; a.u = buf + nx; a.KT = buf + nx + nu; a.N = cfg.N; a.step_us = step_us(cfg);
         a.t0_us = t0_us; a.elapsed_us = elapsed_us; a.substeps = substeps; a.goal = goal ? buf + nx + nu + nk + NX : nullptr; a.ee_z = cfg.ee_on_link_z;
         a.xActual = buf + nx + nu + nk; a.out = dout;
         hipLaunchKernelGGL((k_plant_sim<PD, INTEG, T>), dim3(1), dim3(64), 0, stream, (const void*)model_d, a);
@@ -931,11 +899,7 @@ struct Solver : SolverBase {
             return fail(PDDP_EINVAL, "pddp_simulate_batch: x, u and KT are either all given (host plans) or all NULL (the solution the handle holds)");
         if (substeps < 1) return fail(PDDP_EINVAL, "pddp_simulate_batch: substeps >= 1");
         for (size_t i = 0; i < B; i++) if (!(elapsed_us[i] >= 0)) return fail(PDDP_EINVAL, "pddp_simulate_batch: elapsed_us[" + std::to_string(i) + "] must be >= 0");
-        if (!model_d) {
-            typename PD::Model hm; fill_model(hm, cfg);
-            HIPCHK(hipMalloc(&model_d, sizeof(hm))); allocs.push_back(model_d);
-            HIPCHK(hipMemcpy(model_d, &hm, sizeof(hm), hipMemcpyHostToDevice));
-        }
+        if (int mrc = ensure_model_d()) return mrc;
         const size_t in_bytes = (B * sizeof(In) + 15) / 16 * 16, rec_bytes = in_bytes + B * sizeof(Out);
         if (d_simb_cap < rec_bytes) {
             HIPCHK(hipStreamSynchronize(stream));
@@ -971,7 +935,7 @@ struct Solver : SolverBase {
         }
         HIPCHK(hipMemcpyAsync(d_simb, h_simb, B * sizeof(In), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL((k_plant_sim_batch<PD, INTEG, T>), dim3((unsigned)B), dim3(64), 0, stream, (const void*)model_d, (const In*)d_simb, (Out*)(d_simb + in_bytes), px, pu, pKT, b,
-                           (int)N, cfg.total_time / (cfg.N - 1) * 1000.0 * 1000.0, substeps, goal ? 1 : 0, cfg.ee_on_link_z);
+                           (int)N, step_us(cfg), substeps, goal ? 1 : 0, cfg.ee_on_link_z);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_simb + in_bytes, d_simb + in_bytes, B * sizeof(Out), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));

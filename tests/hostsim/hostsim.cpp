@@ -18,23 +18,9 @@ static constexpr int kMaxPlant = 4;
 static int user_nx() { return -1; }
 static int user_nu() { return -1; }
 #endif
-extern "C" int pddp_state_size(int plant) { return plant == 1 ? 2 : plant == 2 ? 4 : plant == 3 ? 12 : plant == 4 ? 14 : plant == 5 ? user_nx() : -1; }
-extern "C" int pddp_control_size(int plant) { return plant == 1 ? 1 : plant == 2 ? 1 : plant == 3 ? 4 : plant == 4 ? 7 : plant == 5 ? user_nu() : -1; }
-extern "C" int pddp_default_config(pddp_config* c, int plant) {
-    std::memset(c, 0, sizeof(*c));
-    c->plant = plant; c->N = plant == 4 ? 64 : 128; c->M = 4; c->A = (plant == 3 || plant == 4) ? 16 : 32;   /* plant 5 (user plant): the pendulum's defaults */
-    c->integrator = plant == 4 ? 1 : 3; c->batch = 1; c->max_iter = 100; c->ignore_max_rho_exit = 1;
-    c->total_time = plant == 4 ? 0.5 : 4.0; c->alpha_base = (plant == 3 || plant == 4) ? 0.5 : 0.75;
-    c->rho_init = plant == 4 ? 12.5 : (plant == 3 ? 1.0 : 10.0); c->max_defect = plant == 2 ? 0.75 : 1.0;
-    c->tol_cost = 0.0001; c->exp_red_min = 0.05; c->exp_red_max = 1.25;
-    c->Q1 = 0.1; c->Q2 = 0.001; c->R = 0.0001; c->QF1 = 1000.0; c->QF2 = 1000.0;
-    c->Q_EE1 = 0.1; c->Q_EE2 = 0.0; c->QF_EE1 = 1000.0; c->QF_EE2 = 0.0; c->R_EE = 0.0001; c->Q_xEE = 0.0; c->QF_xEE = 0.0; c->Q_xdEE = 0.1; c->QF_xdEE = 1000.0;
-    c->ee_on_link_z = 0.0635;   // plants/cost_arm.cuh:104-115, dynamics_arm.cuh:57-58 (EE_TYPE 1)
-    c->use_finite_diff = 0; c->finite_diff_epsilon = 0.00001;
-    c->use_limits = 0; c->use_smooth_abs = 0; c->smooth_abs_alpha = 0.2;
-    c->ee_type = 1;
-    return 0;
-}
+extern "C" int pddp_state_size(int plant) { return plant == 5 ? user_nx() : builtin_state_size(plant); }
+extern "C" int pddp_control_size(int plant) { return plant == 5 ? user_nu() : builtin_control_size(plant); }
+extern "C" int pddp_default_config(pddp_config* c, int plant) { default_config(c, plant); return 0; }
 
 static Base* mk(const pddp_config& c) {
     switch (c.plant) {
@@ -50,10 +36,7 @@ static Base* mk(const pddp_config& c) {
 }
 extern "C" int pddp_create(const pddp_config* cfg, pddp_handle* out) {
     const pddp_config& c = *cfg;
-    if (c.plant < 1 || c.plant > kMaxPlant) return fail(PDDP_EINVAL, "plant must be 1..4 (5: the user plant of a `make user PLANT_POLICY=...` build)");
-    if (c.N < 4 || (c.N & (c.N - 1)) || c.N > 1024) return fail(PDDP_EINVAL, "N must be a power of two in [4,1024]");
-    if (c.M < 1 || c.N % c.M || c.N / c.M < 2 || c.M > 16) return fail(PDDP_EINVAL, "M must divide N, N/M >= 2, M <= 16");
-    if (c.A < 1 || c.A > 64 || c.batch < 1 || c.max_iter < 1) return fail(PDDP_EINVAL, "A in [1,64], batch >= 1, max_iter >= 1");
+    if (const char* complaint = config_complaint(c, kMaxPlant); complaint[0]) return fail(PDDP_EINVAL, complaint);      // the library's rules, the library's words
     Base* s = mk(c);
     if (!s) return fail(PDDP_EINVAL, "unsupported plant / integrator / dtype combination");
 #ifdef PDDP_HOSTSIM_HAS_USER_PLANT

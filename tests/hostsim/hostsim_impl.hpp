@@ -23,7 +23,7 @@
 #include "../../parallel-ddp_amd/csrc/bp_lg.hpp"
 #include "../../parallel-ddp_amd/csrc/plant_arm_tl.hpp"
 #include "../../parallel-ddp_amd/csrc/mpc.hpp"
-#include "../../parallel-ddp_amd/csrc/iiwa14_model_data.h"
+#include "../../parallel-ddp_amd/csrc/handle_setup.hpp"
 
 using namespace pddp;
 
@@ -54,15 +54,6 @@ struct Base {
 };
 struct pddp_solver { Base* impl; };
 
-template <typename T> static void fill_model(ArmModel<T>& m, const pddp_config& c) {
-    const int v = c.wafr_urdf ? 1 : 0;
-    for (int b = 0; b < 7; b++) { for (int i = 0; i < 36; i++) m.I[36 * b + i] = (T)IIWA14_SPATIAL_INERTIA[v][b][i];
-                                  for (int i = 0; i < 16; i++) m.F[16 * b + i] = (T)IIWA14_JOINT_FRAME[v][b][i]; }
-    m.grav = (T)(c.mpc_mode ? 0.0 : 9.81);
-    arm_model_apply_ee_type(m, c.wafr_urdf, c.ee_type);
-}
-static void fill_model(EmptyModel& m, const pddp_config&) { m.unused = 0; }
-
 template <typename P, int INTEG, typename T>
 struct Sim : Base {
     static constexpr int NX = P::NX, NU = P::NU, NM = NX + NU, NP = P::NPOS;
@@ -71,39 +62,16 @@ struct Sim : Base {
     std::map<std::string, std::pair<void*, size_t>> arrays;
     std::vector<void*> allocs;
     ~Sim() override { for (void* p : allocs) std::free(p); }
-    template <typename U> void al(const char* name, U** out, size_t count) {
-        void* p = std::calloc(count, sizeof(U)); allocs.push_back(p); arrays[name] = {p, count * sizeof(U)}; *out = (U*)p;
+    template <typename U> int al(const char* name, U** out, size_t count) {
+        void* p = std::calloc(count, sizeof(U)); allocs.push_back(p); arrays[name] = {p, count * sizeof(U)}; *out = (U*)p; return 0;
     }
     void init() {
         const pddp_config& c = cfg;
         dm.N = c.N; dm.M = c.M; dm.A = c.A; dm.NB = c.N / c.M;
-        sp.max_iter = c.max_iter; sp.out_stride = c.max_iter + 2; sp.ignore_max_rho_exit = c.ignore_max_rho_exit; sp.tol_cost = c.tol_cost;
-        sp.exp_red_min = c.exp_red_min; sp.exp_red_max = c.exp_red_max; sp.max_defect = c.max_defect; sp.rho_init = c.rho_init; sp.ee_initial_cost_fix = c.ee_initial_cost_fix;
-        cw.Q1 = (T)c.Q1; cw.Q2 = (T)c.Q2; cw.R = (T)c.R; cw.QF1 = (T)c.QF1; cw.QF2 = (T)c.QF2;
-        cw.ee = c.ee_cost; cw.Q_EE1 = (T)c.Q_EE1; cw.Q_EE2 = (T)c.Q_EE2; cw.QF_EE1 = (T)c.QF_EE1; cw.QF_EE2 = (T)c.QF_EE2; cw.R_EE = (T)c.R_EE;
-        cw.Q_xEE = (T)c.Q_xEE; cw.QF_xEE = (T)c.QF_xEE; cw.Q_xdEE = (T)c.Q_xdEE; cw.QF_xdEE = (T)c.QF_xdEE; cw.ee_z = (T)c.ee_on_link_z;
-        cw.fd_eps = c.use_finite_diff ? c.finite_diff_epsilon : 0.0;
-        cw.limits = (P::PLANT == 4) ? c.use_limits : 0;
-        cw.smooth_abs = (P::PLANT == 4 && c.ee_cost) ? c.use_smooth_abs : 0; cw.sa = (T)c.smooth_abs_alpha; cw.sa2 = (T)(c.smooth_abs_alpha * c.smooth_abs_alpha);
-        dt = (T)(c.total_time / (c.N - 1));
-        const size_t B = c.batch, N = c.N, A = c.A, M = c.M;
-#define AL(name, count) al(#name, &b.name, (count))
-        AL(xs, B * A * N * NX); AL(us, B * A * N * NU); AL(ds, B * A * N * NX);
-        AL(xb, B * 2 * N * NX); AL(ucur, B * N * NU); AL(dcur, B * N * NX);
-        AL(P, 2 * B * N * NX * NX); AL(p, 2 * B * N * NX);
-        AL(AB, B * N * NX * NM); AL(H, B * N * NM * NM); AL(g, B * N * NM);
-        AL(KT, B * N * NX * NU); AL(du, B * N * NU); AL(ApBK, B * N * NX * NX); AL(Bdu, B * N * NX);
-        AL(J, B * A); AL(dmax, B * A); AL(dJexp, B * 2 * M); AL(alpha, A); AL(xGoal, B * NX);
-        AL(xTarget, B * NX); AL(costk, B * N); AL(tshift, B);
-        AL(Jout, B * (c.max_iter + 2)); AL(err, B * M); AL(alphaOut, B * (c.max_iter + 2)); AL(state, B);
-#undef AL
-        b.Pp = b.P + B * N * NX * NX; b.pp = b.p + B * N * NX;
-        arrays["P"].second /= 2; arrays["p"].second /= 2;
-        arrays["Pp"] = {b.Pp, arrays["P"].second}; arrays["pp"] = {b.pp, arrays["p"].second};
-        al("x_old", &mb.x_old, B * N * NX); al("u_old", &mb.u_old, B * N * NU); al("KT_old", &mb.KT_old, B * N * NX * NU);
-        for (size_t i = 0; i < A; i++) b.alpha[i] = (T)std::pow(c.alpha_base, (double)i);
+        sp = solver_params_of(c); cw = cost_weights_of<T, P::PLANT>(c); dt = time_step<T>(c);
+        for_each_array<NX, NU>(c, b, mb, arrays, [this](const char* name, auto** out, size_t count) { return al(name, out, count); });
+        alpha_table(c, b.alpha);
         fill_model(model, c); b.model = &model;
-        al("Jpart", &b.Jpart, B * A * M); al("dpart", &b.dpart, B * A * M); al("parts_fresh", &b.parts_fresh, B);
         derive_tl(model);
     }
     // the library's choice of the arm's forward pass / setup implementation (fp_tl.hpp select_fp_path), like fp_coop()
@@ -278,7 +246,7 @@ struct Sim : Base {
         static PlantSimScratch<PD, T> sc;
         typename PD::Model md; fill_model(md, cfg);
         PlantSimArgs<T> a; double out[2] = {0, 0};
-        a.x = (const T*)x; a.u = (const T*)u; a.KT = (const T*)KT; a.N = cfg.N; a.step_us = cfg.total_time / (cfg.N - 1) * 1000.0 * 1000.0;
+        a.x = (const T*)x; a.u = (const T*)u; a.KT = (const T*)KT; a.N = cfg.N; a.step_us = step_us(cfg);
         a.t0_us = t0_us; a.elapsed_us = elapsed_us; a.substeps = substeps; a.goal = (const T*)goal; a.ee_z = cfg.ee_on_link_z; a.xActual = (T*)xActual; a.out = out;
         plant_sim_body<PD, INTEG, T>(this_wave(), sc, &md, a);
         if (avg_err) *avg_err = out[0];
@@ -314,19 +282,11 @@ struct Sim : Base {
         *ptr = it->second.first; *bytes = it->second.second; return 0;
     }
     int get_state(pddp_state* out) override {
-        for (int i = 0; i < cfg.batch; i++) {
-            const auto& s = b.state[i]; pddp_state& o = out[i];
-            o.rho = s.rho; o.drho = s.drho; o.prevJ = s.prevJ; o.dJ = s.dJ; o.z = s.z; o.iter = s.iter; o.alphaIndex = s.alphaIndex;
-            o.ignore_defect = s.ignore_defect; o.accepted = s.accepted; o.done = s.done; o.cur = s.cur; o.cur2 = s.cur2; o.bp_retries = s.bp_retries; o.pw = s.pw;
-        }
+        for (int i = 0; i < cfg.batch; i++) to_public(b.state[i], out[i]);
         return 0;
     }
     int set_state(const pddp_state* in) override {
-        for (int i = 0; i < cfg.batch; i++) {
-            auto& s = b.state[i]; const pddp_state& o = in[i];
-            s.rho = (T)o.rho; s.drho = (T)o.drho; s.prevJ = (T)o.prevJ; s.dJ = (T)o.dJ; s.z = (T)o.z; s.iter = o.iter; s.alphaIndex = o.alphaIndex;
-            s.ignore_defect = o.ignore_defect; s.accepted = o.accepted; s.done = o.done; s.cur = o.cur; s.cur2 = o.cur2; s.bp_retries = o.bp_retries; s.took_step = 0; s.pw = o.pw; s.win_pending = (o.accepted == 1) ? 1 : 0;
-        }
+        for (int i = 0; i < cfg.batch; i++) from_public(in[i], b.state[i]);
         return 0;
     }
     int run_phase(int ph) override {
