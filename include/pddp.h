@@ -138,6 +138,25 @@ int pddp_status(pddp_handle h, int* done, int* iters);
  * x [batch][N][n], u [batch][N][m], KT [batch][N][n*m], Jout/alphaOut [batch][max_iter+2], dmax [batch]. */
 int pddp_store(pddp_handle h, void* x, void* u, void* KT, void* Jout, int* alphaOut, void* dmax);
 
+/* Individual problems ("slots") of a loaded handle, between whole sweeps: a handle with more problems waiting than slots replaces
+ * the finished ones and keeps iterating instead of waiting for its slowest problem (pyddp.solve_stream is that loop).
+ *
+ * pddp_load_problems: x0 [count][N][n], u0 [count][N][m], xGoal [count][n] on the HOST; entry i goes to slot idx[i].  For each named
+ * slot it does what pddp_load(clear_vars = 1) does for that problem on a fresh handle: trajectory and goal uploaded; P, Pp, p, pp, KT,
+ * d, du, err, dmax and the end-effector cost's shift cleared; a fresh solver state (the cost-to-go double buffer in its initial roles:
+ * both halves are zero), Jout[0], alphaOut[0]; the rest of the slot's Jout / alphaOut rows zero; the initial cost and the derivatives
+ * [A B], H, g of the loaded trajectory, computed by the handle's own kernel families on a compact intake area of min(batch, 256)
+ * problems and moved into the slots (larger counts go through it in chunks), so the cost follows `count`, not `batch`.  Nothing that
+ * belongs to another slot changes; the array pointers do not move and no captured graph is rebuilt.  No warm-start arrays, no
+ * forward_rollout: a fresh problem has no previous solution in its slot.  The work is enqueued on the solver's stream behind what is
+ * there; the call synchronises once before it returns.
+ * pddp_store_problems: the rows idx[i] of what pddp_store would return now, compacted to [count][...]; any output may be NULL.  Like
+ * pddp_store it is meaningful between whole sweeps (the sweep that sets `done` also adopts the final step).
+ * Both return PDDP_EINVAL for count < 1, an index outside [0, batch), an index named twice, a NULL idx (pddp_load_problems: any NULL
+ * array) and a handle that pddp_load / pddp_solve never filled -- an unloaded slot has no state to idle in. */
+int pddp_load_problems(pddp_handle h, int count, const int* idx, const void* x0, const void* u0, const void* xGoal, int ignore_first_defect);
+int pddp_store_problems(pddp_handle h, int count, const int* idx, void* x, void* u, void* KT, void* Jout, int* alphaOut, void* dmax);
+
 /* runiLQR_GPU (DDPWrappers.cuh:10-138) for the whole batch: load, init, iterate until every problem exits, store.
  * times_ms[0] = total, [1] = init (load+init+store), like *tTime / *initTime. */
 int pddp_solve(pddp_handle h, void* x0_inout, void* u0_inout, const void* xGoal, void* Jout, int* alphaOut,

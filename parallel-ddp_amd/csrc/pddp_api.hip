@@ -1,6 +1,7 @@
 // libpddp.so: host side of the C ABI declared in include/pddp.h.  gfx950 only; no CPU fallback.
 #include "solver_base.hpp"
 #include "handle_setup.hpp"
+#include "slots.hpp"
 
 static thread_local std::string g_err;
 extern "C" const char* pddp_last_error(void) { return g_err.c_str(); }
@@ -67,6 +68,25 @@ extern "C" int pddp_load_ex(pddp_handle h, const void* x0, const void* u0, const
     IMPL(h);
     if (!x0 || !u0 || !xg) return fail(PDDP_EINVAL, "pddp_load: null trajectory or goal");
     return s->load(x0, u0, xg, KT0, P0, p0, d0, rollout, clear, ifd);
+}
+// individual slots of a loaded handle (slots.hpp): the arguments are checked here, before anything is enqueued
+static int slots_check(SolverBase* s, const char* who, int count, const int* idx) {
+    if (!s->loaded) return fail(PDDP_EINVAL, std::string(who) + ": the handle has never been loaded (the first fill is pddp_load / pddp_solve; an unloaded slot has no state to idle in)");
+    const std::string complaint = pddp::slots_complaint(count, idx, s->cfg.batch);
+    if (!complaint.empty()) return fail(PDDP_EINVAL, std::string(who) + ": " + complaint);
+    return 0;
+}
+extern "C" int pddp_load_problems(pddp_handle h, int count, const int* idx, const void* x0, const void* u0, const void* xg, int ifd) {
+    IMPL(h);
+    if (!idx || !x0 || !u0 || !xg) return fail(PDDP_EINVAL, "pddp_load_problems: null idx, trajectory or goal");
+    if (int rc = slots_check(s, "pddp_load_problems", count, idx)) return rc;
+    return s->load_problems(count, idx, x0, u0, xg, ifd);
+}
+extern "C" int pddp_store_problems(pddp_handle h, int count, const int* idx, void* x, void* u, void* KT, void* Jout, int* alphaOut, void* dmax) {
+    IMPL(h);
+    if (!idx) return fail(PDDP_EINVAL, "pddp_store_problems: null idx");
+    if (int rc = slots_check(s, "pddp_store_problems", count, idx)) return rc;
+    return s->store_problems(count, idx, x, u, KT, Jout, alphaOut, dmax);
 }
 extern "C" int pddp_iterate(pddp_handle h, int sweeps) { IMPL(h); return s->iterate(sweeps); }
 extern "C" int pddp_sync(pddp_handle h) { IMPL(h); return s->sync(); }

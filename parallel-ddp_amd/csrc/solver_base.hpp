@@ -36,6 +36,10 @@ struct SolverBase {
     virtual int sync() = 0;
     virtual int status(int* done, int* iters) = 0;
     virtual int store(void* x, void* u, void* KT, void* Jout, int* alphaOut, void* dmax) = 0;
+    // individual slots of a loaded handle between sweeps (slots.hpp); idx is validated by the caller (pddp_api.hip)
+    virtual int load_problems(int count, const int* idx, const void* x0, const void* u0, const void* xg, int ignore_first_defect) = 0;
+    virtual int store_problems(int count, const int* idx, void* x, void* u, void* KT, void* Jout, int* alphaOut, void* dmax) = 0;
+    bool loaded = false;           // pddp_load / pddp_solve ran: every slot holds a problem (pddp_load_problems replaces problems, it does not fill an empty handle)
     virtual int time_sweeps(int sweeps, float* ms_total, float* ms_phase) = 0;
     virtual int time_kernels(int sweeps, float* ms, char* names, int name_stride) = 0;
     virtual int array(const char* name, void** ptr, size_t* bytes) = 0;

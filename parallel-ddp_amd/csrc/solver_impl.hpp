@@ -4,6 +4,7 @@
 #include "solver_base.hpp"
 #include "kernels.hpp"
 #include "handle_setup.hpp"
+#include "slots.hpp"
 #include "tl_launch.hpp"
 #include "mx_launch.hpp"
 
@@ -44,6 +45,7 @@ struct Solver : SolverBase {
     bool bp_lane_groups = false;
     bool fp_coop = false;          // PDDP_FP=coop
     static constexpr int kNisTl7MaxBatch = 511;   // measured crossover against k_nis_lg (profiles/)
+    bool nis_tl7_batch = false;    // batch <= kNisTl7MaxBatch: a split-rollout handle's setup runs on k_nis_tl7 (a resolved choice like the others: the intake area of a large handle keeps the handle's)
     bool fp_split = false;         // rollouts of a lane-group handle on the split thread-lane kernels (k_fp_tl4 / k_fp_tl2)
     bool fp_two_wave = false;
     bool ls_many = false;          // line search one thread per problem (k_ls_many): from 2048 problems in flight
@@ -162,7 +164,10 @@ struct Solver : SolverBase {
         if (h_simb) hipHostFree(h_simb);
         if (h_stage) hipHostFree(h_stage);
         if (h_state) hipHostFree(h_state);
-        if (stream) hipStreamDestroy(stream);
+        delete intake;
+        if (d_slot_idx) hipFree(d_slot_idx);
+        if (d_slot_stage) hipFree(d_slot_stage);
+        if (stream && !intake_of) hipStreamDestroy(stream);        // (an intake area runs on its handle's stream)
     }
     void register_model(void* dmodel, const ArmModel<T>&) {
         arrays["model_I"] = {dmodel, sizeof(T) * kArmNB * 36};
@@ -190,8 +195,10 @@ struct Solver : SolverBase {
                 return fail(PDDP_EINVAL, "plant 5: the plug-in's gradient routine returns a qdd that differs from its dynamics routine at the same state; the kernel families build the "
                                          "integrators' stage states from either one, so the two have to be the same numbers (call the dynamics routine inside the gradient routine)");
         }
-        HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        if (intake_of) stream = intake_of->stream;
+        else HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         dm.N = c.N; dm.M = c.M; dm.A = c.A; dm.NB = c.N / c.M;
+        nis_tl7_batch = c.batch <= kNisTl7MaxBatch;
         bp_lane_groups = (size_t)c.batch * c.M >= 4096;     // measured crossovers on MI355X (Kuka N=128): wide <= 256 problems < cooperative < 1024 <= lane groups
         bp_wide = (size_t)c.batch * c.M <= 1024 && P::NX >= 12;
         if (const char* v = ksel_fp(cfg)) fp_coop = (std::string(v) == "coop");       // the arm refines this below (derive_tl_model)
@@ -261,6 +268,7 @@ struct Solver : SolverBase {
         b.model = dmodel;
         register_model(dmodel, hm);
         derive_tl_model(hm);
+        if (intake_of) adopt_selection(*intake_of);      // before the arrays below that exist only on some kernel families
         if constexpr (P::PLANT != 4) { if (cf_fp_staged) { b.xw_rec = P::NX + P::NU; if ((rc = alloc("xw", &b.xw, B * N * A * b.xw_rec))) return rc; } }   // records of the staged closed-form rollouts (k_fp_cf)
         if constexpr (P::PLANT == 4) { if (fp_path == kFpTl) { b.xw_rec = 22; if ((rc = alloc("xw", &b.xw, B * N * A * b.xw_rec))) return rc; } }   // knot-major candidate states (fp_tl.hpp)
         if constexpr (P::PLANT == 4) { if (sweep_fused) { if ((rc = alloc("segmap", &b.segmap, B * M * 256))) return rc; } }
@@ -305,6 +313,14 @@ struct Solver : SolverBase {
     }
     int load(const void* x0, const void* u0, const void* xg, const void* KT0, const void* P0, const void* p0, const void* d0, int rollout, int clear,
              int ignore_first_defect) override {
+        if (int rc = enqueue_load(x0, u0, xg, KT0, P0, p0, d0, rollout, clear, ignore_first_defect)) return rc;
+        HIPCHK(hipStreamSynchronize(stream));
+        loaded = true;
+        return 0;
+    }
+    // the whole load on the stream, without the wait (pddp_load_problems enqueues the scatter of the loaded problems behind it)
+    int enqueue_load(const void* x0, const void* u0, const void* xg, const void* KT0, const void* P0, const void* p0, const void* d0, int rollout, int clear,
+                     int ignore_first_defect) {
         const size_t B = cfg.batch, N = cfg.N;
         // current trajectory goes to half 0 of xb (state.cur = 0 after init): one strided copy for the whole batch
         HIPCHK(hipMemcpy2DAsync(b.xb, 2 * N * NX * sizeof(T), x0, N * NX * sizeof(T), N * NX * sizeof(T), B, hipMemcpyHostToDevice, stream));
@@ -332,7 +348,6 @@ struct Solver : SolverBase {
         }
         launch_init_cost_and_setup(stream, ignore_first_defect, rollout, 0);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
     // what starts a solve from the loaded trajectory: initial cost, setup kernel in init mode and, for the end-effector cost, the cost's second pass (its initial cost comes
@@ -443,7 +458,7 @@ struct Solver : SolverBase {
             }
             if (!fp_coop && !cfg.use_finite_diff) {
                 if (part == 0) return;
-                if (fp_split && cfg.batch <= kNisTl7MaxBatch) { launch_nis_tl7<T>(s, tl_variant, b, dm, cw, dt, tl_grav, mode, (int)B); return; }
+                if (fp_split && nis_tl7_batch) { launch_nis_tl7<T>(s, tl_variant, b, dm, cw, dt, tl_grav, mode, (int)B); return; }
                 if (cfg.ee_cost) hipLaunchKernelGGL((k_nis_lg<T, true>), dim3((cfg.N + 31) / 32, B), dim3(256), 0, s, b, dm, cw, dt, mode);
                 else hipLaunchKernelGGL((k_nis_lg<T>), dim3((cfg.N + 31) / 32, B), dim3(256), 0, s, b, dm, cw, dt, mode);
                 return;
@@ -516,7 +531,7 @@ struct Solver : SolverBase {
     int time_kernels(int sweeps, float* ms, char* names, int name_stride) override {
         const bool arm = (P::PLANT == 4), tl = arm && fp_path == kFpTl, lg = arm && !fp_coop;
         const char* nm[6] = {bp_mfma ? "k_bp_mfma" : (arm && bp_lane_groups) ? "k_bp_lg" : cf_bp ? "k_bp_ts" : (gl_bp && cl_bp && mq_bp) ? "k_bp_mq" : (gl_bp && cl_bp) ? "k_bp_cl" : gl_bp ? "k_bp_gl" : bp_wide ? "k_bp_wide" : "k_bp",
-                             (lg && cfg.M > 1 && !maps_in_rollouts()) ? (sweep_fused ? "k_sweep_maps" : sweep_kind == 2 ? "k_sweep_wg" : sweep_kind == 1 ? "k_sweep_st" : "k_sweep_lg") : (cf_records() && cfg.M > 1) ? (mq_fused ? "k_sweep_maps" : "k_sweep_cf") : "", tl ? "k_fp_tl" : (lg && fp_split) ? (fp_two_wave ? "k_fp_tl2" : "k_fp_tl4") : lg ? "k_fp_lg" : (cf_fp && cf_fp_staged) ? "k_fp_cf" : cf_fp ? "k_fp_ts" : "k_fp", ls_in_rollouts() ? "" : ls_many ? "k_ls_many" : "k_ls", "", tl ? "k_nis_tl" : (lg && fp_split && cfg.batch <= kNisTl7MaxBatch) ? "k_nis_tl7" : lg ? "k_nis_lg" : cf_nis ? "k_nis_ts" : (gl_nis && kb_nis) ? "k_nis_kb" : gl_nis ? "k_nis_gl" : "k_nis"};
+                             (lg && cfg.M > 1 && !maps_in_rollouts()) ? (sweep_fused ? "k_sweep_maps" : sweep_kind == 2 ? "k_sweep_wg" : sweep_kind == 1 ? "k_sweep_st" : "k_sweep_lg") : (cf_records() && cfg.M > 1) ? (mq_fused ? "k_sweep_maps" : "k_sweep_cf") : "", tl ? "k_fp_tl" : (lg && fp_split) ? (fp_two_wave ? "k_fp_tl2" : "k_fp_tl4") : lg ? "k_fp_lg" : (cf_fp && cf_fp_staged) ? "k_fp_cf" : cf_fp ? "k_fp_ts" : "k_fp", ls_in_rollouts() ? "" : ls_many ? "k_ls_many" : "k_ls", "", tl ? "k_nis_tl" : (lg && fp_split && nis_tl7_batch) ? "k_nis_tl7" : lg ? "k_nis_lg" : cf_nis ? "k_nis_ts" : (gl_nis && kb_nis) ? "k_nis_kb" : gl_nis ? "k_nis_gl" : "k_nis"};
         static const int phase_of[6] = {PDDP_PHASE_BP, PDDP_PHASE_FP, PDDP_PHASE_FP, PDDP_PHASE_LS, PDDP_PHASE_NIS, PDDP_PHASE_NIS};
         const int part_of[6] = {-1, 0, maps_in_rollouts() ? -1 : 1, -1, 0, 1};      // (a rollout kernel that begins with the sweep is timed as it runs in production)
         HIPCHK(hipStreamSynchronize(stream));
@@ -754,6 +769,127 @@ struct Solver : SolverBase {
         if (KT) HIPCHK(hipMemcpyAsync(KT, b.KT, B * N * NX * NU * sizeof(T), hipMemcpyDeviceToHost, stream));
         if (Jout) HIPCHK(hipMemcpyAsync(Jout, b.Jout, B * (cfg.max_iter + 2) * sizeof(T), hipMemcpyDeviceToHost, stream));
         if (alphaOut) HIPCHK(hipMemcpyAsync(alphaOut, b.alphaOut, B * (cfg.max_iter + 2) * sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    // ---- individual slots of a loaded handle between sweeps: pddp_load_problems / pddp_store_problems (slots.hpp)
+    // The intake area: a second Solver of the same type for min(batch, kSlotIntakeMax) problems on this handle's stream, with this handle's RESOLVED kernel selection
+    // (adopt_selection: the choices init() derives from the batch size are the handle's, not those of a 256-problem handle), created at the first refill.  load() of the
+    // intake is the handle's own init path -- the same kernel families, the same bits; only the init-mode launches ever run on it.
+    Solver* intake = nullptr;
+    const Solver* intake_of = nullptr;             // set on the intake itself: the handle it serves
+    int* d_slot_idx = nullptr;                     // [kSlotIntakeMax] the slot indices of the chunk in flight
+    unsigned char* d_slot_stage = nullptr; size_t d_slot_stage_cap = 0;      // pddp_store_problems: the packed rows of one chunk
+    void adopt_selection(const Solver& o) {
+        nis_tl7_batch = o.nis_tl7_batch; bp_lane_groups = o.bp_lane_groups; fp_coop = o.fp_coop; fp_split = o.fp_split; fp_two_wave = o.fp_two_wave; ls_many = o.ls_many;
+        fp_path = o.fp_path; tl_variant = o.tl_variant; tl_grav = o.tl_grav;
+        cf_bp = o.cf_bp; cf_fp = o.cf_fp; cf_nis = o.cf_nis; gl_bp32 = o.gl_bp32; gl_nis8 = o.gl_nis8; cl_bp = o.cl_bp; mq_bp = o.mq_bp; mq_fused = o.mq_fused;
+        cf_fp_staged = o.cf_fp_staged; kb_nis = o.kb_nis; gl_bp = o.gl_bp; gl_nis = o.gl_nis; cf_serial = o.cf_serial; bp_wide = o.bp_wide;
+        sweep_fused = o.sweep_fused; sweep_kind = o.sweep_kind; bp_mfma = o.bp_mfma;
+    }
+    int slot_chunk() const { return cfg.batch < kSlotIntakeMax ? cfg.batch : kSlotIntakeMax; }
+    int ensure_slot_idx() {
+        if (!d_slot_idx && hipMalloc((void**)&d_slot_idx, kSlotIntakeMax * sizeof(int)) != hipSuccess) return fail(PDDP_ENOMEM, "hipMalloc failed for the slot indices");
+        return 0;
+    }
+    int ensure_intake() {
+        // the arrays that exist only on some kernel families must exist on both sides (pddp_set_array("model_*") can move a handle to another family)
+        if (intake && ((intake->b.xw != nullptr) != (b.xw != nullptr) || intake->b.xw_rec != b.xw_rec || (intake->b.ABc != nullptr) < (b.ABc != nullptr) ||
+                       (intake->b.Hc != nullptr) < (b.Hc != nullptr) || intake->fp_path != fp_path)) {
+            HIPCHK(hipStreamSynchronize(stream));
+            delete intake; intake = nullptr;
+        }
+        if (!intake) {
+            Solver* in = new Solver();
+            in->cfg = cfg; in->cfg.batch = slot_chunk(); in->cfg.use_graph = 0; in->intake_of = this;
+            if (int rc = in->init()) { delete in; return rc; }
+            intake = in;
+        }
+        Solver& in = *intake;
+        in.adopt_selection(*this);
+        in.cw = cw; in.sp = sp; in.dt = dt; in.b.model = b.model; in.h_overridden = h_overridden;
+        if (!b.ABc) { in.b.ABc = nullptr; in.b.Hc = nullptr; }      // the handle left the compact layouts (ab_keep_reference_layout): so does its intake
+        return ensure_slot_idx();
+    }
+    // what a refill moves (copy) or clears (zero) per slot; DESIGN.md "refilling slots" lists the bytes
+    bool refill_table(SlotTable& t) {
+        const Buffers<T>& ib = intake->b;
+        const size_t N = cfg.N, M = cfg.M, A = cfg.A, out = (size_t)cfg.max_iter + 2, e = sizeof(T);
+        t.n = 0; t.N = cfg.N; t.state = nullptr; t.state_stride = t.off_cur = t.off_alpha = 0;
+        bool ok = true;
+        auto copy = [&](const void* c, void* s, size_t cstride, size_t sstride, size_t bytes) { ok = ok && slot_add(t, c, s, cstride, sstride, bytes, kSlotCopy); };
+        auto same = [&](const void* c, void* s, size_t bytes) { copy(c, s, bytes, bytes, bytes); };
+        auto zero = [&](void* s, size_t bytes) { ok = ok && slot_add(t, nullptr, s, 0, bytes, bytes, kSlotZero); };
+        copy(ib.xb, b.xb, 2 * N * NX * e, 2 * N * NX * e, N * NX * e);            // half 0: the fresh state's cur
+        same(ib.ucur, b.ucur, N * NU * e); same(ib.xGoal, b.xGoal, NX * e);
+        same(ib.state, b.state, sizeof(SolverState<T>));
+        same(ib.Jout, b.Jout, out * e); same(ib.alphaOut, b.alphaOut, out * sizeof(int));      // (the intake's rows are zero behind element 0: no sweep ever runs there)
+        if (b.ABc) ok = ok && slot_add_abc(t, ib.ABc, b.ABc, cfg.N, e); else same(ib.AB, b.AB, N * NX * NM * e);
+        same(ib.H, b.H, N * NM * NM * e); same(ib.g, b.g, N * NM * e);
+        if (b.Hc) same(ib.Hc, b.Hc, N * 49 * e);
+        same(ib.costk, b.costk, N * e);
+        zero(b.P, N * NX * NX * e); zero(b.Pp, N * NX * NX * e); zero(b.p, N * NX * e); zero(b.pp, N * NX * e);
+        zero(b.KT, N * NX * NU * e); zero(b.dcur, N * NX * e); zero(b.du, N * NU * e);
+        zero(b.err, M * sizeof(int)); zero(b.dmax, A * e); zero(b.tshift, sizeof(int));
+        return ok;
+    }
+    int load_problems(int count, const int* idx, const void* x0, const void* u0, const void* xg, int ignore_first_defect) override {
+        if (int rc = ensure_intake()) return rc;
+        Solver& in = *intake;
+        SlotTable tab, fetch;
+        if (!refill_table(tab)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
+        fetch.n = 0; fetch.N = cfg.N; fetch.state = nullptr; fetch.state_stride = fetch.off_cur = fetch.off_alpha = 0;
+        if (cfg.ee_cost) slot_add(fetch, in.b.xTarget, b.xTarget, NX * sizeof(T), NX * sizeof(T), NX * sizeof(T), kSlotCopy);      // the slots' own nominal-state targets: read by the setup kernel, not part of a load
+        const size_t N = cfg.N;
+        const int C = slot_chunk();
+        int rc = 0;
+        for (int c0 = 0; c0 < count && !rc; c0 += C) {
+            const int n = count - c0 < C ? count - c0 : C;
+            in.cfg.batch = n;                                        // this chunk's view of the intake area: launches and transfers cover n problems
+            if (hipMemcpyAsync(d_slot_idx, idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, "pddp_load_problems: index transfer failed"); break; }
+            if (fetch.n) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, fetch.n), dim3(256), 0, stream, fetch, (const int*)d_slot_idx, n, (int)cfg.batch, 1);
+            rc = in.enqueue_load((const T*)x0 + (size_t)c0 * N * NX, (const T*)u0 + (size_t)c0 * N * NU, (const T*)xg + (size_t)c0 * NX, nullptr, nullptr, nullptr, nullptr, 0, 1,
+                                 ignore_first_defect);
+            if (!rc) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, tab.n), dim3(256), 0, stream, tab, (const int*)d_slot_idx, n, (int)cfg.batch, 0);
+        }
+        in.cfg.batch = C;
+        if (rc) { hipStreamSynchronize(stream); return rc; }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int store_problems(int count, const int* idx, void* x, void* u, void* KT, void* Jout, int* alphaOut, void* dmax) override {
+        if (int rc = ensure_slot_idx()) return rc;
+        const size_t N = cfg.N, out = (size_t)cfg.max_iter + 2, e = sizeof(T);
+        const int C = slot_chunk();
+        // one staging area per requested output, [C][row] each, 16-byte aligned
+        void* host[6] = {x, u, KT, Jout, alphaOut, dmax};
+        const size_t row[6] = {N * NX * e, N * NU * e, N * NX * NU * e, out * e, out * sizeof(int), e};
+        size_t at[6], need = 0;
+        for (int k = 0; k < 6; k++) { at[k] = need; if (host[k]) need += ((size_t)C * row[k] + 15) / 16 * 16; }
+        if (!need) return 0;
+        if (d_slot_stage_cap < need) {
+            HIPCHK(hipStreamSynchronize(stream));
+            if (d_slot_stage) hipFree(d_slot_stage);
+            d_slot_stage = nullptr; d_slot_stage_cap = 0;
+            if (hipMalloc((void**)&d_slot_stage, need) != hipSuccess) return fail(PDDP_ENOMEM, "pddp_store_problems: hipMalloc failed for the staging buffer");
+            d_slot_stage_cap = need;
+        }
+        SlotTable t;
+        t.n = 0; t.N = cfg.N; t.state = reinterpret_cast<const unsigned char*>(b.state); t.state_stride = sizeof(SolverState<T>);
+        t.off_cur = offsetof(SolverState<T>, cur); t.off_alpha = offsetof(SolverState<T>, alphaIndex);
+        void* src[6] = {b.xb, b.ucur, b.KT, b.Jout, b.alphaOut, b.dmax};
+        const size_t sstride[6] = {2 * row[0], row[1], row[2], row[3], row[4], (size_t)cfg.A * e};
+        const int op[6] = {kSlotCopyHalf, kSlotCopy, kSlotCopy, kSlotCopy, kSlotCopy, kSlotCopyAlpha};
+        int which[6], nw = 0;
+        for (int k = 0; k < 6; k++) if (host[k]) { if (!slot_add(t, d_slot_stage + at[k], src[k], row[k], sstride[k], row[k], op[k])) return fail(PDDP_EINVAL, "pddp_store_problems: internal error (slot table)"); which[nw++] = k; }
+        for (int c0 = 0; c0 < count; c0 += C) {
+            const int n = count - c0 < C ? count - c0 : C;
+            HIPCHK(hipMemcpyAsync(d_slot_idx, idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL((k_slots_gather<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)d_slot_idx, n, (int)cfg.batch);
+            for (int w = 0; w < nw; w++) { const int k = which[w]; HIPCHK(hipMemcpyAsync((unsigned char*)host[k] + (size_t)c0 * row[k], d_slot_stage + at[k], (size_t)n * row[k], hipMemcpyDeviceToHost, stream)); }
+        }
+        HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }

@@ -6,3 +6,4 @@ library) raises.
 """
 from .binding import (PddpConfig, PddpKernelSelection, KERNEL_NAMES, set_kernels, PddpError, Solver, Comm, default_config, library_path, build_id, PLANT_DIMS, algorithmic_bytes, algorithmic_bytes_per_kernel,  # noqa: F401
                       PHASE_BP, PHASE_FP, PHASE_LS, PHASE_NIS, PHASE_INIT_NIS, PHASE_INIT_COST, PHASE_BP_COOP, PHASE_BP_FUSED, PHASE_SWEEP_FUSED, PHASE_ROLLOUT)
+from .stream import SlotScheduler, solve_stream  # noqa: F401

@@ -286,6 +286,27 @@ class Solver:
         self._chk(self.lib.pddp_store(self.h, _p(out["x"]), _p(out["u"]), _p(out["KT"]), _p(out["Jout"]), _p(out["alphaOut"]), _p(out["dmax"])))
         return out
 
+    def load_problems(self, idx, x0, u0, xGoal, ignore_first_defect=1):
+        """pddp_load_problems: fresh problems into the slots idx of a loaded handle (entry i of x0 [count][N][n], u0 [count][N][m], xGoal [count][n] -> slot idx[i])."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        x0, u0, xGoal = self.arr(x0), self.arr(u0), self.arr(xGoal)
+        N, count = self.cfg.N, idx.size
+        assert x0.size == count * N * self.n and u0.size == count * N * self.m and xGoal.size == count * self.n
+        self.lib.pddp_load_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        self._chk(self.lib.pddp_load_problems(self.h, count, _p(idx), _p(x0), _p(u0), _p(xGoal), int(ignore_first_defect)))
+
+    def store_problems(self, idx, only=None):
+        """pddp_store_problems: the rows idx of what store() would return now, [count][...] under the same keys.  only: the keys to fetch (default all)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        K, N, n, m, mi = idx.size, self.cfg.N, self.n, self.m, self.cfg.max_iter
+        out = dict(x=np.zeros((K, N, n), self.dtype), u=np.zeros((K, N, m), self.dtype), KT=np.zeros((K, N, m, n), self.dtype),
+                   Jout=np.zeros((K, mi + 2), self.dtype), alphaOut=np.zeros((K, mi + 2), np.int32), dmax=np.zeros(K, self.dtype))
+        if only is not None:
+            out = {k: v for k, v in out.items() if k in only}
+        self.lib.pddp_store_problems.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        self._chk(self.lib.pddp_store_problems(self.h, K, _p(idx), *[_p(out.get(k)) for k in ("x", "u", "KT", "Jout", "alphaOut", "dmax")]))
+        return out
+
     def solve(self, x0, u0, xGoal, clear_vars=1, ignore_first_defect=1, max_sweeps=None, chunk=8, **load_kw):
         """load -> iterate until every problem has exited -> store (the shape of runiLQR_GPU)."""
         self.load(x0, u0, xGoal, clear_vars, ignore_first_defect, **load_kw)

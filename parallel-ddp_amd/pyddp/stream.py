@@ -1,0 +1,66 @@
+"""A handle as a continuously fed solver: more problems than slots, finished slots refilled between sweeps (pddp_load_problems / pddp_store_problems).
+
+SlotScheduler holds the bookkeeping -- which problem sits in which slot, which slots are padding -- and needs only four methods of a solver: status(), iterate(sweeps),
+load_problems(idx, x0, u0, xGoal, ignore_first_defect) and store_problems(idx), plus load(x0, u0, xGoal) for the first fill; tests drive it with a fake solver on the CPU.
+"""
+import numpy as np
+
+
+class SlotScheduler:
+    """problems: an iterable of (x0, u0, xGoal), each one problem's arrays ([N][n], [N][m], [n], any shape with those sizes).  run() yields (problem index, result) in the
+    order the problems finish; result = that problem's row of store_problems() plus done / iters."""
+
+    def __init__(self, solver, problems, batch, sweeps_per_poll=4, ignore_first_defect=1):
+        self.s, self.it, self.B = solver, iter(problems), int(batch)
+        self.sweeps, self.ifd = max(1, int(sweeps_per_poll)), ignore_first_defect
+        self.owner = [None] * self.B          # slot -> index of the problem it holds; None: padding or already collected
+        self.taken = 0                        # problems drawn from the iterator so far
+
+    def _draw(self, limit):
+        got = []
+        for _ in range(limit):
+            try:
+                got.append(next(self.it))
+            except StopIteration:
+                break
+        return got
+
+    @staticmethod
+    def _stack(probs, k):
+        return np.concatenate([np.asarray(p[k]).ravel() for p in probs])
+
+    def run(self):
+        first = self._draw(self.B)
+        if not first:
+            return
+        for slot in range(len(first)):
+            self.owner[slot] = slot
+        self.taken = len(first)
+        fill = first + [first[0]] * (self.B - len(first))          # a short stream: the empty slots solve copies of the first problem, whose results are dropped
+        self.s.load(self._stack(fill, 0), self._stack(fill, 1), self._stack(fill, 2), clear_vars=1, ignore_first_defect=self.ifd)
+        while any(o is not None for o in self.owner):
+            self.s.iterate(self.sweeps)
+            done, iters = self.s.status()
+            ready = [slot for slot in range(self.B) if self.owner[slot] is not None and done[slot]]
+            if not ready:
+                continue
+            rows = self.s.store_problems(ready)
+            results = [(self.owner[slot], dict({k: v[j] for k, v in rows.items()}, done=int(done[slot]), iters=int(iters[slot]))) for j, slot in enumerate(ready)]
+            fresh = self._draw(len(ready))
+            for slot in ready:
+                self.owner[slot] = None
+            if fresh:
+                into = ready[: len(fresh)]
+                for j, slot in enumerate(into):
+                    self.owner[slot] = self.taken + j
+                self.taken += len(fresh)
+                self.s.load_problems(into, self._stack(fresh, 0), self._stack(fresh, 1), self._stack(fresh, 2), self.ifd)
+            for item in results:
+                yield item
+
+
+def solve_stream(solver, problems, sweeps_per_poll=4, ignore_first_defect=1):
+    """Generator: every problem of `problems` (an iterable of (x0, u0, xGoal)) through `solver`'s slots.  The handle is filled with pddp_load (padded with copies of the
+    first problem when fewer than `batch` are given; their results are dropped), then iterated sweeps_per_poll sweeps at a time; finished slots are stored, refilled from
+    the iterator and yielded as (problem index, result).  Ends when every problem has been yielded."""
+    return SlotScheduler(solver, problems, solver.cfg.batch, sweeps_per_poll, ignore_first_defect).run()
