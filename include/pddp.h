@@ -310,6 +310,11 @@ int pddp_set_state(pddp_handle h, const pddp_state* in /* [batch] */);
 #define PDDP_PHASE_ROLLOUT   9   /* forwardSimKern + costKern + defectKern WITHOUT the sweep: every candidate's segments start from the states that stand in
                                     "xs" at their first knots (fpHelpers.cuh:225-301 teacher-forced from stored start states, e.g. the reference's own)      */
 int pddp_run_phase(pddp_handle h, int phase);
+/* The load stage of pddp_mpc_solve alone: the same argument checks, the same input transfer and the same warm-start kernel (k_mpc_load: shift of the previous solution,
+ * fall-back copies x_old / u_old / KT_old, open-loop rollout from xActual, xGoal / tshift), then a synchronisation -- no initial cost, no setup kernel, no sweep, so
+ * that what the stage leaves in the named arrays can be read before a sweep overwrites P, p, KT, xb and AB (tests/test_mpc_load_stage.py).
+ * xActual, xGoal [batch][n], shift [batch] as for pddp_mpc_solve.  After it: half 0 of "xb" = the rolled-out trajectory, half 1 = the shifted previous one. */
+int pddp_mpc_load(pddp_handle h, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout);
 
 /* Plant plug-in evaluations on the device, `count` independent (x,u) pairs:
  * what = 0 dynamics -> qdd[count][npos]                 (dynamics<T>,          plants/dynamics_*.cuh)

@@ -171,6 +171,11 @@ extern "C" int pddp_mpc_solve(pddp_handle h, const void* xActual, const void* xG
     if (!xActual || !xGoal || !shift) return fail(PDDP_EINVAL, "pddp_mpc_solve: null argument");
     return s->mpc_solve(xActual, xGoal, shift, clear_vars, full_rollout, ifd, max_iter, time_budget_ms, poll_every, x, u, KT, Jout, alphaOut, success, iters);
 }
+extern "C" int pddp_mpc_load(pddp_handle h, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) {
+    IMPL(h);
+    if (!xActual || !xGoal || !shift) return fail(PDDP_EINVAL, "pddp_mpc_load: null argument");
+    return s->mpc_load(xActual, xGoal, shift, clear_vars, full_rollout);
+}
 extern "C" int pddp_get_config(pddp_handle h, pddp_config* out) { IMPL(h); if (!out) return fail(PDDP_EINVAL, "null argument"); *out = s->cfg; return 0; }
 extern "C" int pddp_stream(pddp_handle h, void** hip_stream) { IMPL(h); if (!hip_stream) return fail(PDDP_EINVAL, "null argument"); *hip_stream = (void*)s->stream; return 0; }
 

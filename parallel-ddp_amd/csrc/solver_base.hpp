@@ -58,6 +58,7 @@ struct SolverBase {
     virtual int set_cost_ee(const double* v) = 0;
     virtual int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
                           int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) = 0;
+    virtual int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) = 0;   // mpc_solve's load stage alone (teacher-forcing hook)
     int bench_mode = 0;
     bool h_overridden = false;     // pddp_set_array("H"): the cost Hessian is no longer known to be the plant's own (diagonal for the joint-space cost)
     virtual void drop_graph() = 0;

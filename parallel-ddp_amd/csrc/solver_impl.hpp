@@ -643,23 +643,21 @@ struct Solver : SolverBase {
         drop_graph();
         return 0;
     }
-    int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
-                  int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) override {
+    // The load stage of a control cycle, enqueued: argument checks, pinned staging, the single input transfer and the k_mpc_load launch.  pddp_mpc_solve goes on
+    // from here with the sweeps; pddp_mpc_load (teacher-forcing hook) waits for the stream and returns, so that what k_mpc_load leaves can be read before a sweep
+    // overwrites it.  ONE place selects between the 512-thread pipeline (V = 0 / 1) and the 256-thread kernel.
+    int mpc_enqueue_load(const char* who, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) {
         const size_t B = cfg.batch, N = cfg.N;
-        if (max_iter < 1 || max_iter > cfg.max_iter) return fail(PDDP_EINVAL, "mpc_solve: max_iter must be in [1, config.max_iter]");
-        for (size_t i = 0; i < B; i++) if (shift[i] < 0 || shift[i] >= (int)N - 1) return fail(PDDP_EINVAL, "mpc_solve: shift must be in [0, N-2]");
+        for (size_t i = 0; i < B; i++) if (shift[i] < 0 || shift[i] >= (int)N - 1) return fail(PDDP_EINVAL, std::string(who) + ": shift must be in [0, N-2]");
         if (lean_ctg_ran && !clear_vars)
-            return fail(PDDP_EINVAL, "mpc_solve: this handle iterated with boundary_cost_to_go_only = 1, so its interior cost-to-go slots are stale and a warm start "
+            return fail(PDDP_EINVAL, std::string(who) + ": this handle iterated with boundary_cost_to_go_only = 1, so its interior cost-to-go slots are stale and a warm start "
                                      "(clear_vars = 0) would shift them into the block boundaries; call with clear_vars = 1 once, or create the handle without that option");
         lean_ctg_ran = false;
         if (!mpc_used) { mpc_used = true; drop_graph(); }
-        const double t0 = now_ms();
         // one pinned staging area: pageable host memory would make every small transfer of the cycle a synchronous staging copy of its own
         const size_t out_stride = (size_t)cfg.max_iter + 2;
         const size_t o_state = 0, o_xb = o_state + B * sizeof(SolverState<T>), o_u = o_xb + B * 2 * N * NX * sizeof(T), o_KT = o_u + B * N * NU * sizeof(T),
                      o_J = o_KT + B * N * NX * NU * sizeof(T), o_a = o_J + B * out_stride * sizeof(T), need_bytes = o_a + B * out_stride * sizeof(int) + 16 * B;
-        const size_t rec_state = (sizeof(SolverState<T>) + 15) / 16 * 16;
-        const size_t rec_bytes = (rec_state + (N * NX + N * NU + N * NX * NU + out_stride) * sizeof(T) + out_stride * sizeof(int) + 15) / 16 * 16;   // <= the six separate areas' share per problem
         if (h_stage_bytes < need_bytes) {
             if (h_stage) hipHostFree(h_stage);
             h_stage = nullptr; h_stage_bytes = 0;
@@ -682,6 +680,23 @@ struct Solver : SolverBase {
             }
         }
         if (!split_roll) hipLaunchKernelGGL((k_mpc_load<P, INTEG, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
+        return 0;
+    }
+    int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) override {
+        if (int rc = mpc_enqueue_load("mpc_load", xActual, xGoal, shift, clear_vars, full_rollout)) return rc;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
+                  int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) override {
+        const size_t B = cfg.batch, N = cfg.N;
+        if (max_iter < 1 || max_iter > cfg.max_iter) return fail(PDDP_EINVAL, "mpc_solve: max_iter must be in [1, config.max_iter]");
+        const double t0 = now_ms();
+        if (int rc = mpc_enqueue_load("mpc_solve", xActual, xGoal, shift, clear_vars, full_rollout)) return rc;
+        const size_t out_stride = (size_t)cfg.max_iter + 2;
+        const size_t rec_state = (sizeof(SolverState<T>) + 15) / 16 * 16;
+        const size_t rec_bytes = (rec_state + (N * NX + N * NU + N * NX * NU + out_stride) * sizeof(T) + out_stride * sizeof(int) + 15) / 16 * 16;   // <= the six separate areas' share per problem
         const int saved_max_iter = sp.max_iter;
         sp.max_iter = max_iter;                                  // acceptRejectTrajGPU(..., max_iter)
         launch_init_cost_and_setup(stream, ifd, 0, 1);

@@ -483,6 +483,13 @@ class Solver:
     def run_phase(self, phase):
         self._chk(self.lib.pddp_run_phase(self.h, int(phase)))
 
+    def mpc_load(self, xActual, xGoal, shift, clear_vars=0, full_rollout=1):
+        """pddp_mpc_load: the load stage of mpc_solve alone (shift, fall-back copies, open-loop rollout); read what it leaves with get()."""
+        xActual, xGoal = self.arr(xActual), self.arr(xGoal)
+        shift = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.int32), (self.cfg.batch,)))
+        self.lib.pddp_mpc_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.pddp_mpc_load(self.h, _p(xActual), _p(xGoal), _p(shift), int(clear_vars), int(full_rollout)))
+
     def plant_eval_paths(self):
         """`what` codes of pddp_plant_eval per plant function: every implementation of the plant the library carries."""
         if self.cfg.plant != 4:

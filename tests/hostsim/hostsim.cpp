@@ -105,6 +105,10 @@ extern "C" int pddp_mpc_solve(pddp_handle h, const void* xActual, const void* xG
                               int max_iter, double, int, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) {
     return h->impl->mpc_solve(xActual, xGoal, shift, clear_vars, full_rollout, ifd, max_iter, x, u, KT, Jout, alphaOut, success, iters);
 }
+extern "C" int pddp_mpc_load(pddp_handle h, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) {
+    if (!xActual || !xGoal || !shift) return fail(PDDP_EINVAL, "pddp_mpc_load: null argument");
+    return h->impl->mpc_load(xActual, xGoal, shift, clear_vars, full_rollout);
+}
 extern "C" int pddp_simulate(pddp_handle h, const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps, const void* goal, void* xa,
                              double* avg_err, int* failed) { return h->impl->simulate(x, u, KT, t0_us, elapsed_us, substeps, goal, xa, avg_err, failed); }
 extern "C" int pddp_ee_pos(pddp_handle h, int count, const void* x, void* out) { return h->impl->ee_pos(count, x, out); }

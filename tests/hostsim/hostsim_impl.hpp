@@ -49,6 +49,7 @@ struct Base {
     virtual int run_phase(int) = 0;
     virtual int plant_eval(int, int, const void*, const void*, void*) = 0;
     virtual int mpc_solve(const void*, const void*, const int*, int, int, int, int, void*, void*, void*, void*, int*, int*, int*) = 0;
+    virtual int mpc_load(const void*, const void*, const int*, int, int) = 0;
     virtual int simulate(const void*, const void*, const void*, double, double, int, const void*, void*, double*, int*) = 0;
     virtual int ee_pos(int, const void*, void*) = 0;
 };
@@ -215,18 +216,26 @@ struct Sim : Base {
         if (cfg.ee_cost) for (size_t pb = 0; pb < B; pb++) init_cost_body<P, T>(w, cost_k.data(), b, dm, cw, sp, ifd, rollout, (int)pb, 2, 0);
         return 0;
     }
+    // what k_mpc_load does for every problem of the handle (pddp_mpc_load; the first stage of mpc_solve below)
+    int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) override {
+        const size_t B = cfg.batch; const Wave w = this_wave();
+        for (size_t i = 0; i < B; i++) if (shift[i] < 0 || shift[i] >= cfg.N - 1) return fail(PDDP_EINVAL, "mpc_load: shift must be in [0, N-2]");
+        std::memcpy(b.xGoal, xGoal, B * NX * sizeof(T));
+        static MpcScratch<P, T> ms;
+        for (size_t pb = 0; pb < B; pb++) {
+            mpc_load_body<P, INTEG, T>(w, ms, b, mb, dm, dt, (int)pb, (const T*)xActual + pb * NX, shift[pb], clear_vars, full_rollout);
+            b.tshift[pb] = (cfg.ee_cost && cfg.ee_cost_shift) ? shift[pb] : 0;
+        }
+        return 0;
+    }
     int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter,
                   void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) override {
         const size_t B = cfg.batch; const Wave w = this_wave();
         if (max_iter < 1 || max_iter > cfg.max_iter) return fail(PDDP_EINVAL, "mpc_solve: max_iter must be in [1, config.max_iter]");
-        std::memcpy(b.xGoal, xGoal, B * NX * sizeof(T));
-        static MpcScratch<P, T> ms; std::vector<T> cost_k(cfg.N);
+        if (int rc = mpc_load(xActual, xGoal, shift, clear_vars, full_rollout)) return rc;
+        std::vector<T> cost_k(cfg.N);
         const int saved = sp.max_iter; sp.max_iter = max_iter;
-        for (size_t pb = 0; pb < B; pb++) {
-            mpc_load_body<P, INTEG, T>(w, ms, b, mb, dm, dt, (int)pb, (const T*)xActual + pb * NX, shift[pb], clear_vars, full_rollout);
-            b.tshift[pb] = (cfg.ee_cost && cfg.ee_cost_shift) ? shift[pb] : 0;
-            init_cost_body<P, T>(w, cost_k.data(), b, dm, cw, sp, ifd, 0, (int)pb, cfg.ee_cost ? 1 : 0, 1);
-        }
+        for (size_t pb = 0; pb < B; pb++) init_cost_body<P, T>(w, cost_k.data(), b, dm, cw, sp, ifd, 0, (int)pb, cfg.ee_cost ? 1 : 0, 1);
         phase(PDDP_PHASE_INIT_NIS);
         if (cfg.ee_cost) for (size_t pb = 0; pb < B; pb++) init_cost_body<P, T>(w, cost_k.data(), b, dm, cw, sp, ifd, 0, (int)pb, 2, 1);
         for (int guard = 0; guard < 100000; guard++) {

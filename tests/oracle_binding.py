@@ -273,14 +273,14 @@ class Oracle:
 class OracleMpc:
     """Persistent GPU-semantics solver state of the oracle for the MPC wrapper (ora_gs_*)."""
 
-    def __init__(self, cfg, dtype=np.float64):
-        self.c, self.dtype, self.suf = cfg, np.dtype(dtype), _suf(dtype)
+    def __init__(self, cfg, dtype=np.float64, variant="strict"):
+        self.c, self.dtype, self.suf, self.variant = cfg, np.dtype(dtype), _suf(dtype), variant
         self.npos, self.n, self.m = PLANT_DIMS[cfg.plant]
-        f = getattr(lib(), f"ora_gs_create_{self.suf}"); f.restype = C.c_void_p
+        f = getattr(lib(variant), f"ora_gs_create_{self.suf}"); f.restype = C.c_void_p
         self.h = C.c_void_p(f(C.byref(cfg)))
 
     def _f(self, name):
-        return getattr(lib(), f"ora_gs_{name}_{self.suf}")
+        return getattr(lib(self.variant), f"ora_gs_{name}_{self.suf}")
 
     def set_traj(self, x, u):
         x, u = np.ascontiguousarray(x, self.dtype), np.ascontiguousarray(u, self.dtype)
