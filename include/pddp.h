@@ -192,6 +192,26 @@ int pddp_set_ee_cost_shift(pddp_handle h, int on);
  * the cost gradient and Hessian of the current trajectory are rebuilt there.  Arm plant only (the other plants' weights are
  * constants of plants/cost_{pend,cart,quad}.cuh). */
 int pddp_set_cost(pddp_handle h, double Q1, double Q2, double R, double QF1, double QF2);
+/* Cost weights per problem (arm plant).  The record is the handle's cost family's own, in the argument order of the handle-wide call:
+ *   joint-space cost (ee_cost = 0): 5 doubles  Q1 Q2 R QF1 QF2                                        (pddp_set_cost)
+ *   end-effector cost (ee_cost = 1): 9 doubles Q_EE1 Q_EE2 QF_EE1 QF_EE2 R_EE Q_xEE QF_xEE Q_xdEE QF_xdEE (pddp_set_cost_ee)
+ * The records take effect the way pddp_set_cost's do: they are in force for the following loads and solves, and the cost, gradient and
+ * Hessian of a trajectory already in a slot are NOT rebuilt by the call -- follow it with pddp_load / pddp_load_ex / pddp_solve /
+ * pddp_solve_ex / pddp_mpc_solve for the whole handle or pddp_load_problems for the named slots.  (Sweeping a running problem between
+ * the call and its reload mixes old derivatives with new weights, as after pddp_set_cost: not checked.)  Problems that are not named
+ * keep their weights; running problems in other slots are untouched.
+ * The first call gives the handle a device table [batch][record] in its element type, every row the handle-wide record, and drops the
+ * captured sweep graph once; later calls only write rows (on the solver's stream, one synchronisation before the call returns).  A
+ * handle that never calls it behaves exactly as without this entry point.  pddp_set_cost / pddp_set_cost_ee afterwards overwrite
+ * EVERY row with the new handle-wide record (the last call wins); pddp_get_config keeps reporting the handle-wide record.
+ * pddp_get_cost_problems: what the device holds for the named problems, widened to double (before the first per-problem call: the
+ * handle-wide record for every index).
+ * pddp_cost_record_size: 5 or 9.  All three return PDDP_EINVAL for a plant other than the arm (the other plants' weights are constants)
+ * and for a plug-in cost; the setter and the getter also, with the handle unchanged, for count < 1, a NULL idx or w, an index outside
+ * [0, batch), an index named twice and (setter) a weight that is not finite.  The handle need not be loaded yet. */
+int pddp_cost_record_size(pddp_handle h);
+int pddp_set_cost_problems(pddp_handle h, int count, const int* idx, const double* w /* [count][record] */);
+int pddp_get_cost_problems(pddp_handle h, int count, const int* idx, double* w /* [count][record] */);
 /* ---- the lock-step experiment around the solver ------------------------- */
 /* simulateForward<T, SUBSTEPS> (examples/WAFR_MPC_examples.cu:111-139): the simulated robot of the lock-step MPC experiment.  Starting
  * from xActual at plant time t0_us (the plan's t0), integrates the plant IN DOUBLE for elapsed_us in `substeps` steps under the trajectory

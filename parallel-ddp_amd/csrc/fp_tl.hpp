@@ -232,12 +232,12 @@ PDDP_HD void arm_tl_rollout_segment(const ArmTlModel<T>& md, T grav, const Buffe
         tl_load14(xr, xcur + (size_t)kn * NX);
 #pragma unroll
         for (int i = 0; i < NU; i++) { ucv[i] = uc[(size_t)kn * NU + i]; duv[i] = du[(size_t)kn * NU + i]; }
-        tl_rollout_step<T>(r, md, grav, b, dm, cw, dt, k, Kk, xr, ucv, duv, xg, sink);
+        tl_rollout_step<T>(r, md, grav, b, dm, cost_weights_at(b, cw, pb), dt, k, Kk, xr, ucv, duv, xg, sink);      // (the problem's own record, fetched where it is used)
     }
     T ucN[NU];
 #pragma unroll
     for (int i = 0; i < NU; i++) ucN[i] = uc[(size_t)(N - 1) * NU + i];
-    tl_rollout_end<T>(r, dm, cw, ucN, xg, sink);
+    tl_rollout_end<T>(r, dm, cost_weights_at(b, cw, pb), ucN, xg, sink);
     if (part) {
         const size_t slot = (size_t)pb * dm.A + a_idx;
         b.Jpart[slot * dm.M + seg] = r.J; b.dpart[slot * dm.M + seg] = r.sdef;
@@ -333,8 +333,9 @@ PDDP_HD void tl_reduce_parts(const Buffers<T>& b, const Dims& dm, int pb) {
 // four-byte stores 84 bytes apart per lane; store_xu = false: likewise the adopted state and control, which the caller then finds in x, u).  Returns 0: nothing moved,
 // 4: trajectory adopted only (final accepted step), 1: g computed but no Jacobian wanted (terminal knot), 3: g and Jacobian.
 template <typename T>
-PDDP_HD int arm_tl_nis_cost_vals(const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw, int mode, int k, int pb, T* x, T* u, T* gl, bool store_xu = true) {
+PDDP_HD int arm_tl_nis_cost_vals(const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw_, int mode, int k, int pb, T* x, T* u, T* gl, bool store_xu = true) {
     constexpr int NX = 14, NU = 7, NM = 21;
+    const CostWeights<T> cw = cost_weights_at(b, cw_, pb);              // (thread = knot: a wave may hold knots of several problems)
     const int N = dm.N;
     const SolverState<T>& st = b.state[pb];
     const size_t knot = (size_t)pb * N + k;
@@ -400,7 +401,7 @@ PDDP_HD bool tl_ee_rpy_weighted(const CostWeights<T>& cw) { return cw.Q_EE2 != T
 // one rollout step with the end-effector cost: control law, the tool point of the CURRENT state, the seven per-joint running sums (costFunc with s_cost: joint 0 also takes
 // the end-effector term), dynamics, Euler step.  Every segment runs NB steps; the last one's final step (knot N - 1) only evaluates the cost (forwardSimInner :236, :259-265).
 template <typename T, typename Sink>
-PDDP_HD void tl_rollout_step_ee(TlRollout<T>& r, T* acc, const ArmTlModel<T>& md, T grav, const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw, T dt, int k,
+PDDP_HD void tl_rollout_step_ee(TlRollout<T>& r, T* acc, const ArmTlModel<T>& md, T grav, const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw_, T dt, int k,
                                 const T* Kk, const T* xr, const T* uc, const T* du, const T* goal, const T* xt, int tshift, const Sink& sink) {
     constexpr int NX = 14, NU = 7;
     const int kn = r.kStart + k, N = dm.N;
@@ -413,6 +414,7 @@ PDDP_HD void tl_rollout_step_ee(TlRollout<T>& r, T* acc, const ArmTlModel<T>& md
         ArmTlFrames<T> fr;
         arm_tl_world_chain<false, T>(md, st.c, st.s, fr);
         T pos[6];
+        const CostWeights<T> cw = cost_weights_at(b, cw_, r.pb);        // per lane: whether roll / pitch / yaw carry a weight is the problem's own business
         arm_tl_tool_point<T>(fr, cw.ee_z, tl_ee_rpy_weighted<T>(cw), pos);
 #pragma unroll
         for (int ind = 0; ind < NU; ind++) {
@@ -511,9 +513,10 @@ PDDP_HD bool arm_tl_nis_cost_ee(const ArmTlModel<T>& md, const Buffers<T>& b, co
     return arm_tl_nis_cost_ee_knot<T>(md, b, dm, cw, mode, k, pb, x, u);
 }
 template <typename T>
-PDDP_HD bool arm_tl_nis_cost_ee_knot(const ArmTlModel<T>& md, const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw, int mode, int k, int pb, const T* x, const T* u,
+PDDP_HD bool arm_tl_nis_cost_ee_knot(const ArmTlModel<T>& md, const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw_, int mode, int k, int pb, const T* x, const T* u,
                                      bool h_block_only) {
     constexpr int NX = 14, NM = 21, NP = 7;
+    const CostWeights<T> cw = cost_weights_at(b, cw_, pb);
     const int N = dm.N;
     const size_t knot = (size_t)pb * N + k;
     const bool fin = (k == N - 1), fin_ee = k >= N - 1 - b.tshift[pb];

@@ -50,6 +50,7 @@ __global__ void k_fp(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int init_ro
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int a_idx = blockIdx.x, pb = blockIdx.y, M = dm.M;
     if (init_rollout != 1 && !fp_active<T>(b, dm, pb)) return;
+    if constexpr (P::PLANT == 4) cw = cost_weights_at(b, cw, pb);     // the problem's own weights (pb is blockIdx.y: uniform, scalar loads)
     using L = FpLds<P, T>;
     unsigned char* ptr = lds_raw;
     SweepScratch<P, T>& sw = *reinterpret_cast<SweepScratch<P, T>*>(ptr); ptr += L::align16(sizeof(SweepScratch<P, T>));
@@ -98,6 +99,7 @@ __global__ __launch_bounds__(MAXT, 1) void k_fp_lg(Buffers<T> b, Dims dm, CostWe
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int pb = blockIdx.x;
     if (!init_rollout && !fp_active<T>(b, dm, pb)) return;
+    cw = cost_weights_at(b, cw, pb);                         // the problem's own weights (uniform: scalar loads)
     const int A_all = init_rollout ? 1 : dm.A, A_eff = A_all / (int)gridDim.y, a0 = (int)blockIdx.y * A_eff, n_inst = A_eff * dm.M;
     __shared__ ArmModel<T> lds_model;
     T* cost_k = reinterpret_cast<T*>(lds_raw);              // [A_eff][N]
@@ -142,6 +144,7 @@ __global__ __launch_bounds__(256, 2) void k_nis_lg(Buffers<T> b, Dims dm, CostWe
     __syncthreads();
     const int k = blockIdx.x * 32 + (threadIdx.x >> 3), pb = blockIdx.y;
     if (k >= dm.N || LgDevice<T>::lane() == 7) return;       // lane 7 of every group stays inactive (lanegroup.hpp)
+    cw = cost_weights_at(b, cw, pb);                         // the problem's own weights (uniform: scalar loads)
     ArmLgConst<LgDevice<T>> c;
     arm_lg_load_const<LgDevice<T>, T>(c, &lds_model);
     arm_lg_nis_body<LgDevice<T>, T, EE>(c, b, dm, cw, dt, mode, k, pb);
@@ -202,10 +205,18 @@ __global__ __launch_bounds__(64) void k_ls_many(Buffers<T> b, Dims dm, SolverPar
 }
 
 // next-iteration setup: grid (N, B), block 64 (see nis_body).
-template <typename P, int INTEG, typename T>
+// PC (the arm with per-problem cost weights, Buffers::cwt): an instantiation of its own.  The body's out-of-line cost routines take the record by reference, so the
+// problem's own record needs an address: it is put into LDS (every lane stores the same uniform values; 88 / 168 bytes), not into a private copy, which would live
+// in scratch.  The instantiation without a table hands the kernel argument on as it always did.
+template <typename P, int INTEG, typename T, bool PC = false>
 __global__ __launch_bounds__(64) void k_nis(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int mode) {
     __shared__ NisScratch<P, INTEG, T> s;
-    nis_body<P, INTEG, T>(this_wave(), s, b, dm, cw, dt, mode, blockIdx.x, blockIdx.y);
+    if constexpr (PC) {
+        __shared__ CostWeights<T> own;
+        own = cost_weights_at(b, cw, (int)blockIdx.y);                                // the problem's own weights (uniform: scalar loads)
+        wsync();
+        nis_body<P, INTEG, T>(this_wave(), s, b, dm, own, dt, mode, blockIdx.x, blockIdx.y);
+    } else nis_body<P, INTEG, T>(this_wave(), s, b, dm, cw, dt, mode, blockIdx.x, blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------------------------- closed-form plants, many problems in flight: thread-serial kernels
@@ -875,6 +886,7 @@ __global__ __launch_bounds__(64) void k_hc_expand(Buffers<T> b, int knots, int N
     const int G = blockIdx.x * 64 + threadIdx.x;
     if (G >= knots || (G % N) == N - 1) return;
     T* H = b.H + (size_t)G * 441; const T* hc = b.Hc + (size_t)G * 49;
+    if (b.cwt) { T Qx; cost_diag_weights_at<T>(b.cwt, 1, G / N, Qx, Qxd, Ru); }      // per-problem weights: the knot's problem's own diagonal
     for (int e = 0; e < 441; e++) {
         const int c = e / 21, r = e % 21;
         H[e] = (r < 7 && c < 7) ? hc[c * 7 + r] : (r != c ? T(0) : (r < 14 ? Qxd : Ru));
@@ -977,6 +989,7 @@ template <typename P, typename T>
 __global__ __launch_bounds__(64) void k_init_cost(Buffers<T> b, Dims dm, CostWeights<T> cw, SolverParams sp, int ignore_first_defect, int rollout,
                                                   int stage, int keep_alpha) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    if constexpr (P::PLANT == 4) cw = cost_weights_at(b, cw, (int)blockIdx.x);      // the problem's own weights (uniform: scalar loads)
     init_cost_body<P, T>(this_wave(), reinterpret_cast<T*>(lds_raw), b, dm, cw, sp, ignore_first_defect, rollout, blockIdx.x, stage, keep_alpha);
 }
 

@@ -12,7 +12,7 @@ namespace pddp {
 // b.ABc non-null (and diag_h): [A B] is read from the compact array (ab_compact.hpp), dt rebuilds its constant rows.  keep_P: write every knot's cost-to-go
 // (the default; phase hook, MPC handles); otherwise only the block-boundary slots the next pass reads (pddp_config.boundary_cost_to_go_only).
 template <typename T>
-void launch_bp_mfma(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batch, bool diag_h, T hq1, T hq2, T hr, T dt, bool keep_P, bool fuse_sweep);
+void launch_bp_mfma(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batch, bool diag_h, T hq1, T hq2, T hr, T dt, bool keep_P, bool fuse_sweep, int ee = 0);
 // fuse_sweep (and b.segmap): the pass composes every shooting segment's sweep map instead of writing A - B K / B du; launch_sweep_maps then replaces the sweep kernel
 template <typename T>
 void launch_sweep_maps(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batch);

@@ -2,6 +2,7 @@
 #include "solver_base.hpp"
 #include "handle_setup.hpp"
 #include "slots.hpp"
+#include "cost_table.hpp"
 
 static thread_local std::string g_err;
 extern "C" const char* pddp_last_error(void) { return g_err.c_str(); }
@@ -98,6 +99,29 @@ extern "C" int pddp_time_kernels(pddp_handle h, int sweeps, float* ms6, char* na
     return s->time_kernels(sweeps, ms6, names, name_stride);
 }
 extern "C" int pddp_set_cost(pddp_handle h, double Q1, double Q2, double R, double QF1, double QF2) { IMPL(h); return s->set_cost(Q1, Q2, R, QF1, QF2); }
+// per-problem cost weights (cost_table.hpp): every argument is checked here, before the handle is touched
+static int cost_problems_check(SolverBase* s, const char* who, int count, const int* idx, const double* w, bool check_w) {
+    const int rec = s->cost_record_size();
+    if (!rec) return fail(PDDP_EINVAL, std::string(who) + ": per-problem cost weights belong to the KUKA arm's own cost families (plant 4); the other plants' weights are constants");
+    const std::string complaint = pddp::cost_records_complaint(count, idx, w, s->cfg.batch, rec, check_w);
+    if (!complaint.empty()) return fail(PDDP_EINVAL, std::string(who) + ": " + complaint);
+    return 0;
+}
+extern "C" int pddp_cost_record_size(pddp_handle h) {
+    IMPL(h);
+    const int rec = s->cost_record_size();
+    return rec ? rec : fail(PDDP_EINVAL, "pddp_cost_record_size: per-problem cost weights belong to the KUKA arm's own cost families (plant 4)");
+}
+extern "C" int pddp_set_cost_problems(pddp_handle h, int count, const int* idx, const double* w) {
+    IMPL(h);
+    if (int rc = cost_problems_check(s, "pddp_set_cost_problems", count, idx, w, true)) return rc;
+    return s->set_cost_problems(count, idx, w);
+}
+extern "C" int pddp_get_cost_problems(pddp_handle h, int count, const int* idx, double* w) {
+    IMPL(h);
+    if (int rc = cost_problems_check(s, "pddp_get_cost_problems", count, idx, w, false)) return rc;
+    return s->get_cost_problems(count, idx, w);
+}
 extern "C" int pddp_simulate(pddp_handle h, const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps, const void* goal_xyz,
                              void* xActual_inout, double* avg_err, int* failed) {
     IMPL(h); if (!x || !u || !KT || !xActual_inout) return fail(PDDP_EINVAL, "null argument");

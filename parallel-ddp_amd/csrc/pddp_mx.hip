@@ -31,24 +31,53 @@ __global__ __launch_bounds__(64) void k_bp_mfma_f64(Buffers<double> b, Dims dm, 
     if (inst >= batch * dm.M) return;
     arm_mx_bp_block<double, FS, DIAGH, CAB, FUSE, HQQ>(lds, b, dm, inst / dm.M, inst % dm.M, hq1, hq2, hr, dt, flags);
 }
+// Per-problem cost weights (Buffers::cwt, plants.hpp): the same block with the diagonal of the running knots' cost Hessian taken from the problem's own row of the table
+// instead of the launch arguments -- read once per wavefront in front of the knot loop, by scalar loads (the problem index comes from blockIdx).  Entry points of their
+// own: a handle without a table launches k_bp_mfma / k_bp_mfma_f64 as it always did.  Only the DIAGH instantiations exist (the others read H, which the setup kernel
+// wrote from the table).  ee: the table holds end-effector records (nine weights; the diagonal is Q_xEE, Q_xdEE, R_EE).
+// (the three numbers are the same in every lane; readfirstlane says so to the compiler, which then keeps them in scalar registers like the launch arguments they replace)
+__device__ __forceinline__ float mx_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ double mx_uniform(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+template <bool FS, bool CAB, bool FUSE, bool HQQ = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PDDP_MX_WAVES_OF(CAB, HQQ), PDDP_MX_WAVES_OF(CAB, HQQ)))) void k_bp_mfma_pc(Buffers<float> b, Dims dm, int batch, int ee, float dt, int flags) {
+    __shared__ __attribute__((aligned(16))) float lds[kMxLds + kMxDmaFloats];
+    const int inst = blockIdx.x;
+    if (inst >= batch * dm.M) return;
+    float hq1, hq2, hr;
+    cost_diag_weights_at<float>(b.cwt, ee, inst / dm.M, hq1, hq2, hr);
+    arm_mx_bp_block<float, FS, true, CAB, FUSE, HQQ>(lds, b, dm, inst / dm.M, inst % dm.M, mx_uniform(hq1), mx_uniform(hq2), mx_uniform(hr), dt, flags);
+}
+template <bool FS, bool CAB, bool FUSE, bool HQQ = false>
+__global__ __launch_bounds__(64) void k_bp_mfma_f64_pc(Buffers<double> b, Dims dm, int batch, int ee, double dt, int flags) {
+    __shared__ __attribute__((aligned(16))) double lds[kMxLds];
+    const int inst = blockIdx.x;
+    if (inst >= batch * dm.M) return;
+    double hq1, hq2, hr;
+    cost_diag_weights_at<double>(b.cwt, ee, inst / dm.M, hq1, hq2, hr);
+    arm_mx_bp_block<double, FS, true, CAB, FUSE, HQQ>(lds, b, dm, inst / dm.M, inst % dm.M, mx_uniform(hq1), mx_uniform(hq2), mx_uniform(hr), dt, flags);
+}
 template <bool FS, bool DIAGH, bool CAB, bool FUSE, bool HQQ = false>
-static void launch_one(hipStream_t s, unsigned n, const Buffers<float>& b, const Dims& dm, int batch, float hq1, float hq2, float hr, float dt, int kp) {
+static void launch_one(hipStream_t s, unsigned n, const Buffers<float>& b, const Dims& dm, int batch, float hq1, float hq2, float hr, float dt, int kp, int ee) {
+    if constexpr (DIAGH) { if (b.cwt) { hipLaunchKernelGGL((k_bp_mfma_pc<FS, CAB, FUSE, HQQ>), dim3(n), dim3(64), 0, s, b, dm, batch, ee, dt, kp); return; } }
     hipLaunchKernelGGL((k_bp_mfma<FS, DIAGH, CAB, FUSE, HQQ>), dim3(n), dim3(64), 0, s, b, dm, batch, hq1, hq2, hr, dt, kp);
 }
 template <bool FS, bool DIAGH, bool CAB, bool FUSE, bool HQQ = false>
-static void launch_one(hipStream_t s, unsigned n, const Buffers<double>& b, const Dims& dm, int batch, double hq1, double hq2, double hr, double dt, int kp) {
+static void launch_one(hipStream_t s, unsigned n, const Buffers<double>& b, const Dims& dm, int batch, double hq1, double hq2, double hr, double dt, int kp, int ee) {
+    if constexpr (DIAGH) { if (b.cwt) { hipLaunchKernelGGL((k_bp_mfma_f64_pc<FS, CAB, FUSE, HQQ>), dim3(n), dim3(64), 0, s, b, dm, batch, ee, dt, kp); return; } }
     hipLaunchKernelGGL((k_bp_mfma_f64<FS, DIAGH, CAB, FUSE, HQQ>), dim3(n), dim3(64), 0, s, b, dm, batch, hq1, hq2, hr, dt, kp);
 }
 
 template <typename T>
-void launch_bp_mfma(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batch, bool diag_h, T hq1, T hq2, T hr, T dt, bool keep_P, bool fuse_sweep) {
+void launch_bp_mfma(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batch, bool diag_h, T hq1, T hq2, T hr, T dt, bool keep_P, bool fuse_sweep, int ee) {
     const unsigned n = (unsigned)batch * dm.M;
     const int kp = (keep_P ? kMxKeepP : 0) | ((fuse_sweep && b.segmap) ? kMxFuseSweep : 0);
     const bool cab = b.ABc != nullptr && diag_h;
-#define PDDP_MX_LAUNCH(FS, DH, CB, FU) launch_one<FS, DH, CB, FU>(s, n, b, dm, batch, hq1, hq2, hr, dt, kp)
+#define PDDP_MX_LAUNCH(FS, DH, CB, FU) launch_one<FS, DH, CB, FU>(s, n, b, dm, batch, hq1, hq2, hr, dt, kp, ee)
     const bool fu = (kp & kMxFuseSweep) != 0;
     if (cab && b.Hc) {                                                // end-effector handles on the thread-lane / matrix-core path: compact [A B] + the compact position block
-#define PDDP_MX_LAUNCH_Q(FS, FU) launch_one<FS, true, true, FU, true>(s, n, b, dm, batch, hq1, hq2, hr, dt, kp)
+#define PDDP_MX_LAUNCH_Q(FS, FU) launch_one<FS, true, true, FU, true>(s, n, b, dm, batch, hq1, hq2, hr, dt, kp, ee)
         if (dm.M > 1) { if (fu) PDDP_MX_LAUNCH_Q(true, true); else PDDP_MX_LAUNCH_Q(true, false); }
         else PDDP_MX_LAUNCH_Q(false, false);
 #undef PDDP_MX_LAUNCH_Q
@@ -65,8 +94,8 @@ void launch_bp_mfma(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batc
     }
 #undef PDDP_MX_LAUNCH
 }
-template void launch_bp_mfma<float>(hipStream_t, const Buffers<float>&, const Dims&, int, bool, float, float, float, float, bool, bool);
-template void launch_bp_mfma<double>(hipStream_t, const Buffers<double>&, const Dims&, int, bool, double, double, double, double, bool, bool);
+template void launch_bp_mfma<float>(hipStream_t, const Buffers<float>&, const Dims&, int, bool, float, float, float, float, bool, bool, int);
+template void launch_bp_mfma<double>(hipStream_t, const Buffers<double>&, const Dims&, int, bool, double, double, double, double, bool, bool, int);
 
 // k_sweep_maps: grid ceil(B / PER), block 64.  The forward sweep from the per-segment maps the backward pass composed (bp_mfma.hpp kMxFuseSweep): e <- Phi_s e + gamma_s over the
 // segments for the s-sequence (gamma = the map's column 14) and the t-sequence (gamma = the defect of the segment's boundary knot: it enters at the segment's last

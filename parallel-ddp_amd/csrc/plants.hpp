@@ -9,6 +9,7 @@
 
 #include "plant_arm.hpp"
 #include "plant_closed_form.hpp"
+#include "solver_state.hpp"
 
 namespace pddp {
 
@@ -24,6 +25,40 @@ struct CostWeights {   // arm joint-space weights (plants/cost_arm.cuh:97-103); 
     T sa;
     double fd_eps;          // > 0: USE_FINITE_DIFF with this FINITE_DIFF_EPSILON (config.cuh:68-71): [A B] by central differences (integrators.hpp); rides here because every setup kernel takes this record
 };
+
+// Per-problem cost weights (pddp_set_cost_problems): Buffers::cwt is null (every problem carries the handle-wide record `cw`, a kernel argument) or a table
+// [batch][record] in the handle's element type, the record in the argument order of the handle-wide call of the handle's cost family:
+//     joint-space cost   5: Q1 Q2 R QF1 QF2                                               (pddp_set_cost)
+//     end-effector cost  9: Q_EE1 Q_EE2 QF_EE1 QF_EE2 R_EE Q_xEE QF_xEE Q_xdEE QF_xdEE    (pddp_set_cost_ee)
+// cost_weights_at: the record of problem pb -- `cw` with exactly the family's weight fields replaced from row pb; ee, ee_z, limits, smooth_abs, sa, sa2 and fd_eps
+// are the handle's whatever the table holds.  Where pb comes from blockIdx the row is uniform over the wave and arrives by scalar loads.  (Record lengths and the
+// diagonal the matrix-core backward pass takes: solver_state.hpp, next to Buffers.)
+// (Written field by field: a copy of the whole record with rows stored over it afterwards leaves a piece of the record in private memory -- 16 bytes of scratch
+// per lane in every kernel that calls it.)
+template <typename T>
+PDDP_HD CostWeights<T> cost_weights_at(const Buffers<T>& b, const CostWeights<T>& cw, int pb) {
+    const bool t = b.cwt != nullptr, je = t && !cw.ee, ee = t && cw.ee;
+    const T* r = b.cwt + (size_t)pb * (cw.ee ? kCostRecEe : kCostRecJoint);      // (dereferenced only behind je / ee)
+    CostWeights<T> o;
+    o.Q1 = je ? r[0] : cw.Q1; o.Q2 = je ? r[1] : cw.Q2; o.R = je ? r[2] : cw.R; o.QF1 = je ? r[3] : cw.QF1; o.QF2 = je ? r[4] : cw.QF2;
+    o.ee = cw.ee;
+    o.Q_EE1 = ee ? r[0] : cw.Q_EE1; o.Q_EE2 = ee ? r[1] : cw.Q_EE2; o.QF_EE1 = ee ? r[2] : cw.QF_EE1; o.QF_EE2 = ee ? r[3] : cw.QF_EE2; o.R_EE = ee ? r[4] : cw.R_EE;
+    o.Q_xEE = ee ? r[5] : cw.Q_xEE; o.QF_xEE = ee ? r[6] : cw.QF_xEE; o.Q_xdEE = ee ? r[7] : cw.Q_xdEE; o.QF_xdEE = ee ? r[8] : cw.QF_xdEE;
+    o.ee_z = cw.ee_z; o.limits = cw.limits; o.smooth_abs = cw.smooth_abs; o.sa2 = cw.sa2; o.sa = cw.sa; o.fd_eps = cw.fd_eps;
+    return o;
+}
+
+// `cw` with the five joint-space weights taken from r[0..5) (a row of the table, or a copy of one in LDS); field by field, like cost_weights_at
+template <typename T>
+PDDP_HD CostWeights<T> cost_weights_joint_row(const CostWeights<T>& cw, const T* r) {
+    CostWeights<T> o;
+    o.Q1 = r[0]; o.Q2 = r[1]; o.R = r[2]; o.QF1 = r[3]; o.QF2 = r[4];
+    o.ee = cw.ee;
+    o.Q_EE1 = cw.Q_EE1; o.Q_EE2 = cw.Q_EE2; o.QF_EE1 = cw.QF_EE1; o.QF_EE2 = cw.QF_EE2; o.R_EE = cw.R_EE;
+    o.Q_xEE = cw.Q_xEE; o.QF_xEE = cw.QF_xEE; o.Q_xdEE = cw.Q_xdEE; o.QF_xdEE = cw.QF_xdEE;
+    o.ee_z = cw.ee_z; o.limits = cw.limits; o.smooth_abs = cw.smooth_abs; o.sa2 = cw.sa2; o.sa = cw.sa; o.fd_eps = cw.fd_eps;
+    return o;
+}
 
 // USE_LIMITS_FLAG (plants/cost_arm.cuh:13-94): limitCosts<T, dLevel>(s_x, s_u, ind, k) = qr * quadPen<T, dLevel>(val, limit) -- qr = Q_PL = Q_VL = R_TL = 100, the
 // limits of the iiwa scaled by the safety factors 0.8 (getPosLimit / getVelLimit / getTorqueLimit), quadPen = 0 inside the limit, else 0.5 d^2 | sign(val) d | 1

@@ -56,6 +56,10 @@ struct SolverBase {
     virtual int ee_pos(int count, const void* x, void* out) = 0;
     virtual int set_cost(double Q1, double Q2, double R, double QF1, double QF2) = 0;
     virtual int set_cost_ee(const double* v) = 0;
+    // per-problem cost weights of the arm (cost_table.hpp); the arguments are validated by the caller (pddp_api.hip)
+    virtual int cost_record_size() const = 0;      // 5 (joint-space cost) or 9 (end-effector cost); 0: the handle's plant has no weights to set
+    virtual int set_cost_problems(int count, const int* idx, const double* w) = 0;
+    virtual int get_cost_problems(int count, const int* idx, double* w) = 0;
     virtual int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
                           int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) = 0;
     virtual int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) = 0;   // mpc_solve's load stage alone (teacher-forcing hook)

@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 #include "handle_setup.hpp"
 #include "slots.hpp"
+#include "cost_table.hpp"
 #include "tl_launch.hpp"
 #include "mx_launch.hpp"
 
@@ -91,7 +92,7 @@ struct Solver : SolverBase {
     int h_view() override {
         if constexpr (P::PLANT == 4) {
             if (b.Hc) {
-                hipLaunchKernelGGL((k_hc_expand<T>), dim3((cfg.batch * cfg.N + 63) / 64), dim3(64), 0, stream, b, (int)(cfg.batch * cfg.N), cfg.N, hw[1], hw[2]);
+                hipLaunchKernelGGL((k_hc_expand<T>), dim3((cfg.batch * cfg.N + 63) / 64), dim3(64), 0, stream, b, (int)(cfg.batch * cfg.N), cfg.N, hw[1], hw[2]);      // (with per-problem weights: every problem's own, from the table)
                 HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(stream));
             }
         }
@@ -477,6 +478,7 @@ struct Solver : SolverBase {
             }
         }
         if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) { if (gl_nis) { if (gl_nis8) hipLaunchKernelGGL((k_nis_gl<P, INTEG, T, 8>), dim3((B * cfg.N + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); else hipLaunchKernelGGL((k_nis_gl<P, INTEG, T, 16>), dim3((B * cfg.N + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); return; } }
+        if constexpr (P::PLANT == 4) { if (b.cwt) { hipLaunchKernelGGL((k_nis<P, INTEG, T, true>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); return; } }
         hipLaunchKernelGGL((k_nis<P, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode);
     }
     void launch_sweep(hipStream_t s, int only = -1, int store_candidates = 0, int part = -1) {
@@ -491,7 +493,7 @@ struct Solver : SolverBase {
                     const bool ee = cfg.ee_cost != 0;
                     const bool diag_h = !h_overridden && (!ee || b.Hc != nullptr);
                     launch_bp_mfma<T>(s, b, dm, (int)B, diag_h, hw[0], hw[1], hw[2], dt, keep_all_ctg() || store_candidates,
-                                      sweep_fused && (!store_candidates || phase_fused_sweep));
+                                      sweep_fused && (!store_candidates || phase_fused_sweep), ee ? 1 : 0);      // (per-problem weights: the diagonal comes from the table, not from hw)
                 }
             }
             if constexpr (P::PLANT == 4) { if (lane_groups && !bp_mfma) hipLaunchKernelGGL((k_bp_lg<T>), dim3((B * cfg.M + kLgPerWave - 1) / kLgPerWave), dim3(64), 0, s, b, dm, (int)B); }
@@ -633,7 +635,7 @@ struct Solver : SolverBase {
         cfg.Q1 = Q1; cfg.Q2 = Q2; cfg.R = R; cfg.QF1 = QF1; cfg.QF2 = QF2;
         cw = cost_weights_of<T, P::PLANT>(cfg);
         if (graph) { hipGraphExecDestroy(graph); graph = nullptr; graph_mode = -1; }   // the weights are kernel arguments baked into the captured sweep
-        return 0;
+        return fill_cost_table();
     }
     int set_cost_ee(const double* v) override {
         if (!cfg.ee_cost) return fail(PDDP_EINVAL, "pddp_set_cost_ee: the handle was not created with ee_cost = 1");
@@ -641,6 +643,65 @@ struct Solver : SolverBase {
         cfg.Q_EE1 = v[0]; cfg.Q_EE2 = v[1]; cfg.QF_EE1 = v[2]; cfg.QF_EE2 = v[3]; cfg.R_EE = v[4]; cfg.Q_xEE = v[5]; cfg.QF_xEE = v[6]; cfg.Q_xdEE = v[7]; cfg.QF_xdEE = v[8];
         cw = cost_weights_of<T, P::PLANT>(cfg);
         drop_graph();
+        return fill_cost_table();
+    }
+    // ---- per-problem cost weights (cost_table.hpp, plants.hpp cost_weights_at): pddp_set_cost_problems / pddp_get_cost_problems
+    // The table exists from the first pddp_set_cost_problems on; until then b.cwt is null and every kernel takes the handle-wide record from its arguments, as it always did.
+    // Its creation changes which kernels a sweep launches (the matrix-core backward pass and the thread-lane kernels have instantiations of their own) and a kernel
+    // argument, so the captured graph goes ONCE; afterwards the graph holds the pointer and a call only writes rows, on the stream, behind what is enqueued there.
+    T* d_cwt = nullptr;
+    std::vector<T> cwt_stage;                      // host rows of the call in flight (the call waits for the stream before it returns)
+    int cost_record_size() const override { return P::PLANT == 4 && !P::kPluginCost ? cost_record_len(cfg.ee_cost) : 0; }
+    // every row <- the handle-wide record (a table that exists: pddp_set_cost / pddp_set_cost_ee after per-problem weights; the last call wins)
+    int fill_cost_table() {
+        if (!d_cwt) return 0;
+        const int rec = cost_record_len(cfg.ee_cost);
+        cwt_stage.resize((size_t)cfg.batch * rec);
+        for (int i = 0; i < cfg.batch; i++) cost_record_of<T>(cw, cwt_stage.data() + (size_t)i * rec);
+        HIPCHK(hipMemcpyAsync(d_cwt, cwt_stage.data(), cwt_stage.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int ensure_cost_table(int rows) {
+        if (d_cwt) return 0;
+        void* p = nullptr;
+        if (hipMalloc(&p, (size_t)rows * cost_record_len(cfg.ee_cost) * sizeof(T)) != hipSuccess) return fail(PDDP_ENOMEM, "hipMalloc failed for the per-problem cost weights");
+        allocs.push_back(p); d_cwt = (T*)p;
+        return 0;
+    }
+    int set_cost_problems(int count, const int* idx, const double* w) override {
+        const int rec = cost_record_len(cfg.ee_cost);
+        if (!d_cwt) {
+            if (int rc = ensure_cost_table(cfg.batch)) return rc;
+            if (int rc = fill_cost_table()) return rc;                 // (waits for the stream: nothing in flight reads the old argument set)
+            b.cwt = d_cwt;
+            drop_graph();
+        }
+        // contiguous runs of slots go up in one transfer each; rows that are not named keep their values
+        cwt_stage.resize((size_t)count * rec);
+        cost_records_pack<T>(count, rec, w, cwt_stage.data());
+        for (int i = 0; i < count;) {
+            int j = i + 1;
+            while (j < count && idx[j] == idx[j - 1] + 1) j++;
+            HIPCHK(hipMemcpyAsync(d_cwt + (size_t)idx[i] * rec, cwt_stage.data() + (size_t)i * rec, (size_t)(j - i) * rec * sizeof(T), hipMemcpyHostToDevice, stream));
+            i = j;
+        }
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int get_cost_problems(int count, const int* idx, double* w) override {
+        const int rec = cost_record_len(cfg.ee_cost);
+        cwt_stage.resize((size_t)count * rec);
+        if (d_cwt) {                                                   // contiguous runs of slots come down in one transfer each, as the setter sends them up
+            for (int i = 0; i < count;) {
+                int j = i + 1;
+                while (j < count && idx[j] == idx[j - 1] + 1) j++;
+                HIPCHK(hipMemcpyAsync(cwt_stage.data() + (size_t)i * rec, d_cwt + (size_t)idx[i] * rec, (size_t)(j - i) * rec * sizeof(T), hipMemcpyDeviceToHost, stream));
+                i = j;
+            }
+            HIPCHK(hipStreamSynchronize(stream));
+        } else for (int i = 0; i < count; i++) cost_record_of<T>(cw, cwt_stage.data() + (size_t)i * rec);
+        for (size_t e = 0; e < (size_t)count * rec; e++) w[e] = (double)cwt_stage[e];
         return 0;
     }
     // The load stage of a control cycle, enqueued: argument checks, pinned staging, the single input transfer and the k_mpc_load launch.  pddp_mpc_solve goes on
@@ -823,6 +884,10 @@ struct Solver : SolverBase {
         Solver& in = *intake;
         in.adopt_selection(*this);
         in.cw = cw; in.sp = sp; in.dt = dt; in.b.model = b.model; in.h_overridden = h_overridden;
+        if (b.cwt && !in.b.cwt) {                                    // per-problem cost weights: the intake area gets a table of its own, filled per chunk from the slots' rows (load_problems)
+            if (int rc = in.ensure_cost_table(slot_chunk())) return rc;
+            in.b.cwt = in.d_cwt;
+        }
         if (!b.ABc) { in.b.ABc = nullptr; in.b.Hc = nullptr; }      // the handle left the compact layouts (ab_keep_reference_layout): so does its intake
         return ensure_slot_idx();
     }
@@ -855,6 +920,10 @@ struct Solver : SolverBase {
         if (!refill_table(tab)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
         fetch.n = 0; fetch.N = cfg.N; fetch.state = nullptr; fetch.state_stride = fetch.off_cur = fetch.off_alpha = 0;
         if (cfg.ee_cost) slot_add(fetch, in.b.xTarget, b.xTarget, NX * sizeof(T), NX * sizeof(T), NX * sizeof(T), kSlotCopy);      // the slots' own nominal-state targets: read by the setup kernel, not part of a load
+        if (b.cwt) {                                                 // ... and their own cost weights: rows idx[c0 .. c0 + n) of the handle's table -> rows 0 .. n of the intake's
+            const size_t rb = cost_record_len(cfg.ee_cost) * sizeof(T);
+            if (!slot_add(fetch, in.d_cwt, d_cwt, rb, rb, rb, kSlotCopy)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
+        }
         const size_t N = cfg.N;
         const int C = slot_chunk();
         int rc = 0;

@@ -20,6 +20,8 @@
 //   Jout[B][max_iter+2] alphaOut[B][max_iter+2]     the reference's observables
 #pragma once
 
+#include <cstddef>
+
 #include "pddp_common.hpp"
 
 namespace pddp {
@@ -70,7 +72,19 @@ struct Buffers {
     int *err, *alphaOut;
     SolverState<T>* state;
     const void* model;   // plant constants (P::Model) in device memory
+    const T* cwt;        // [B][5 | 9] per-problem cost weights of the arm (plants.hpp cost_weights_at); null: every problem carries the handle-wide record, a kernel argument
 };
+
+// Rows of Buffers::cwt (plants.hpp cost_weights_at): 5 weights of the joint-space cost, 9 of the end-effector cost, in the argument order of pddp_set_cost / pddp_set_cost_ee.
+constexpr int kCostRecJoint = 5, kCostRecEe = 9;
+PDDP_HD int cost_record_len(int ee) { return ee ? kCostRecEe : kCostRecJoint; }
+// the three weights the running knots' cost Hessian is the diagonal of (positions, velocities, controls): what the matrix-core backward pass and the API view of the
+// compact end-effector block take instead of reading H -- joint-space cost Q1 Q2 R, end-effector cost Q_xEE Q_xdEE R_EE
+template <typename T>
+PDDP_HD void cost_diag_weights_at(const T* cwt, int ee, int pb, T& hq1, T& hq2, T& hr) {
+    const T* r = cwt + (size_t)pb * cost_record_len(ee);
+    if (ee) { hq1 = r[5]; hq2 = r[7]; hr = r[4]; } else { hq1 = r[0]; hq2 = r[1]; hr = r[2]; }
+}
 
 // rho schedule: bpHelpers.cuh:500-501, nisInitHelpers.cuh:494 (up) and :508 (down)
 template <typename T> PDDP_HD void rho_increase(SolverState<T>& s) {

@@ -307,6 +307,31 @@ class Solver:
         self._chk(self.lib.pddp_store_problems(self.h, K, _p(idx), *[_p(out.get(k)) for k in ("x", "u", "KT", "Jout", "alphaOut", "dmax")]))
         return out
 
+    def cost_record_size(self):
+        """pddp_cost_record_size: 5 (joint-space cost: Q1 Q2 R QF1 QF2) or 9 (end-effector cost: the arguments of set_cost_ee in order); arm handles only."""
+        rc = self.lib.pddp_cost_record_size(self.h)
+        if rc <= 0:
+            self._chk(rc if rc else -1)
+        return rc
+
+    def set_cost_problems(self, idx, w):
+        """pddp_set_cost_problems: cost weights per problem -- record i of w (len(idx) x cost_record_size() doubles, any shape) for slot idx[i]; in force for the
+        following loads and solves (follow it with load() or load_problems(idx, ...)); the other slots keep theirs."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        w = np.ascontiguousarray(w, dtype=np.float64).ravel()
+        if w.size != idx.size * self.cost_record_size():
+            raise PddpError(f"set_cost_problems: {idx.size} slots need {idx.size * self.cost_record_size()} weights ({self.cost_record_size()} per record), got {w.size}")
+        self.lib.pddp_set_cost_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_cost_problems(self.h, idx.size, _p(idx), _p(w)))
+
+    def get_cost_problems(self, idx):
+        """pddp_get_cost_problems: [len(idx)][cost_record_size()] doubles, what the device holds for those slots (the handle-wide record before any set_cost_problems)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        w = np.zeros((idx.size, self.cost_record_size()), np.float64)
+        self.lib.pddp_get_cost_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_get_cost_problems(self.h, idx.size, _p(idx), _p(w)))
+        return w
+
     def solve(self, x0, u0, xGoal, clear_vars=1, ignore_first_defect=1, max_sweeps=None, chunk=8, **load_kw):
         """load -> iterate until every problem has exited -> store (the shape of runiLQR_GPU)."""
         self.load(x0, u0, xGoal, clear_vars, ignore_first_defect, **load_kw)

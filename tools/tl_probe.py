@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Resources + static instruction mix of the two thread-lane kernels bench.py times (k_fp_tl<float,1,false,false>, k_nis_tl<float,1,false,true>) from a REDUCED copy of
-csrc/pddp_tl.hip (the launchers' explicit instantiations removed, the two kernels instantiated explicitly): compiles in ~15 s instead of ~90.
+csrc/pddp_tl.hip + csrc/pddp_tl_nis.hip (the launchers' explicit instantiations removed, the two kernels instantiated explicitly): compiles in ~15 s instead of ~90.
 usage: tools/tl_probe.py [-D... | other compiler flags]      several flag sets separated by '--' run in parallel"""
 import collections, os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mx_isa
 pkg = mx_isa.pkg
-src = open(os.path.join(pkg, "csrc", "pddp_tl.hip")).read()
+src = open(os.path.join(pkg, "csrc", "pddp_tl.hip")).read() + "\n" + open(os.path.join(pkg, "csrc", "pddp_tl_nis.hip")).read()
 src = "\n".join(l for l in src.splitlines() if not l.startswith("template void launch_"))
 src += """
 namespace pddp {
