@@ -181,6 +181,37 @@ int pddp_solve_ex(pddp_handle h, void* x0_inout, void* u0_inout, const void* xGo
 int pddp_mpc_solve(pddp_handle h, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout,
                    int ignore_first_defect, int max_iter, double time_budget_ms, int poll_every, void* x, void* u, void* KT, void* Jout,
                    int* alphaOut, int* success, int* iters);
+/* Control cycles for NAMED slots of a loaded handle: a handle that serves many robots receives their measurements at different times and control rates.
+ * xActual, xGoal [count][n], shift [count] on the HOST; entry i belongs to slot idx[i].  Outputs [count][...], the rows pddp_mpc_solve returns (any may be NULL).
+ *
+ * Named slots.  For slot idx[i] the call does exactly what pddp_mpc_solve does for that problem on the whole handle, with entry i of the inputs: shift or clear of the
+ * previous solution the slot holds and the fall-back copies, the rollout from xActual, xGoal and the end-effector cost's shift, initial cost and setup with alphaIndex
+ * kept, the iLQR loop under this call's max_iter and time budget (measured from the start of the call), the fall-back when no step was taken.  Afterwards every
+ * array pddp_get_array names holds for the named slots what the whole-handle call would have left there, BIT FOR BIT -- the pddp_state record, x_old, u_old, KT_old,
+ * Jout, alphaOut and the candidates xs, us, ds included (the call's staging record "mpc_out" is the one exception: it belongs to the call, not to a slot).
+ * Unnamed slots.  Nothing that belongs to an unnamed slot changes, bit for bit: its arrays, its state record, its row of the cost table -- whether the slot has exited
+ * or is still running.  Array pointers do not move.
+ * Handle-wide effects are those of pddp_mpc_solve: from the first MPC use of the handle on, sweeps write every cost-to-go slot (the captured sweep graph is dropped
+ * there, once, and nowhere else), and a warm start (clear_vars = 0) is refused after sweeps with boundary_cost_to_go_only, with pddp_mpc_solve's message.  Here
+ * clear_vars = 1 clears the named slots only, so it is accepted but does NOT lift that refusal: it stays in force, for every slot, until pddp_mpc_solve or
+ * pddp_mpc_load with clear_vars = 1 has cleared the whole handle.  Per-problem
+ * cost rows (pddp_set_cost_problems), xTarget and the handle-wide weights are in force for the named slots, as in pddp_load_problems.
+ * How.  No kernel skips problems.  Per chunk of up to min(batch, 256) named slots the slots' state is gathered into the handle's intake area (the one pddp_load_problems
+ * uses), the intake runs the cycle it would run as a handle of that many problems -- the handle's resolved kernel families, the code pddp_mpc_solve runs --, and every
+ * per-problem array is scattered back to its slot.  The cost follows `count`, not `batch`.  Larger counts go through in chunks, in order.  The work is enqueued on the
+ * solver's stream behind what is there; without a budget and with poll_every >= max_iter each chunk synchronises once.
+ * Both return PDDP_EINVAL and leave the handle unchanged for count < 1, a NULL idx / xActual / xGoal / shift, an index outside [0, batch) or named twice, a shift
+ * outside [0, N-2], max_iter outside [1, config.max_iter] (pddp_mpc_solve_problems) and a handle that pddp_load / pddp_solve never filled. */
+int pddp_mpc_solve_problems(pddp_handle h, int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout,
+                            int ignore_first_defect, int max_iter, double time_budget_ms, int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut,
+                            int* success, int* iters);
+/* teacher-forcing hook, the slot form of pddp_mpc_load: the load stage alone for the named slots, results left in the slots */
+int pddp_mpc_load_problems(pddp_handle h, int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout);
+/* Measurement hook of the two calls above, like pddp_time_kernels for a sweep (tools/mpc_slots_time.py, profiles/mpc_slots.md): a caller cannot put events between
+ * the stages of a call from outside.  timing = 1 / 0: record HIP events around the three stages of every chunk of the following calls / stop (-1: keep); it changes
+ * nothing of what the calls compute or launch.  ms3, when not NULL, receives the last timed call's stream time in ms, summed over its chunks: [0] in (movers + load
+ * stage kernel), [1] cycle (initial cost, setup, sweeps, fall-back), [2] out (movers). */
+int pddp_mpc_slots_profile(pddp_handle h, int timing, float* ms3);
 /* End-effector cost weights for the following loads / solves (costParams of runiLQR_MPC_GPU, MPCHelpers.cuh:118-135); requires a
  * handle created with ee_cost = 1. */
 int pddp_set_cost_ee(pddp_handle h, double Q_EE1, double Q_EE2, double QF_EE1, double QF_EE2, double R_EE, double Q_xEE, double QF_xEE,

@@ -956,6 +956,30 @@ __global__ __launch_bounds__(512) void k_mpc_load(Buffers<T> b, MpcBuffers<T> mb
     mpc_load_body<P, INTEG, T, V>(this_wave(), s, b, mb, dm, dt, blockIdx.x, xActual + (size_t)blockIdx.x * P::NX, shift[blockIdx.x], clear_vars, full_rollout,
                                   (int)threadIdx.x >> 6, (int)blockDim.x >> 6, pipe);
 }
+// The warm start of named slots gathers while it shifts (pddp_mpc_solve_problems): grid (n), block as k_mpc_load.  Block i reads the previous solution from slot idx[i] of
+// the handle's buffers hb (read only) and writes the shifted or cleared arrays, the fall-back copies and the rollout into problem i of the intake area b / mb -- instead
+// of a plain gather of P, Pp, p, pp, KT, xb, u, d into the intake followed by k_mpc_load shifting them in place there, which moves the largest arrays of a problem twice.
+// In the 512-thread pipeline the shifting waves run beside the serial rollout, the critical path: the gather rides there.  Everything else of a slot (state, derivatives,
+// candidates, ...) comes in through k_slots_scatter before this kernel.
+template <typename P, int INTEG, typename T, int V = -1>
+__global__ __launch_bounds__(512) void k_mpc_load_slots(Buffers<T> b, MpcBuffers<T> mb, Buffers<T> hb, const int* __restrict__ idx, int batch, Dims dm, T dt, const T* xActual,
+                                                        const int* shift, int clear_vars, int full_rollout, const T* goal_in, int tshift_mode) {
+    __shared__ MpcScratch<P, T> s;
+    const int q = idx[blockIdx.x];
+    if (q < 0 || q >= batch) return;                               // (uniform per block, before any barrier; validated on the host: a stale index must not become a stray read)
+    if (threadIdx.x < P::NX) b.xGoal[(size_t)blockIdx.x * P::NX + threadIdx.x] = goal_in[(size_t)blockIdx.x * P::NX + threadIdx.x];
+    if (threadIdx.x == 0) b.tshift[blockIdx.x] = tshift_mode ? shift[blockIdx.x] : 0;
+    float* pipe = nullptr;
+    if constexpr (P::PLANT == 4 && INTEG == 1 && V >= 0 && sizeof(T) == 4) {
+        __shared__ __attribute__((aligned(16))) float pipe_lds[kPipeLdsOpenLoop / 4];
+        pipe = pipe_lds;
+        if (threadIdx.x < kPipeFlags) tl_pipe_lds(pipe, false).flag[threadIdx.x] = 0;
+        __syncthreads();
+    }
+    const MpcPrev<T> prev = mpc_prev_of<T>(hb, dm, P::NX, P::NU, (size_t)q);
+    mpc_load_body<P, INTEG, T, V, true>(this_wave(), s, b, mb, dm, dt, blockIdx.x, xActual + (size_t)blockIdx.x * P::NX, shift[blockIdx.x], clear_vars, full_rollout,
+                                        (int)threadIdx.x >> 6, (int)blockDim.x >> 6, pipe, &prev);
+}
 // out != null: the problem's results packed into one record of rec_bytes for a single transfer back -- [SolverState, padded to 16 bytes][x: current half][u][K]
 // [Jout: out_stride][alphaOut: out_stride ints]; a problem that took no step packs the fall-back arrays it has just been restored from (the same values).
 template <typename P, typename T>

@@ -17,41 +17,10 @@
 #include "fp_pipe.hpp"
 #include "plant_arm_lg.hpp"
 #include "solver_state.hpp"
+#include "mpc_move.hpp"
 
 namespace pddp {
 
-template <typename T>
-struct MpcBuffers {      // extra arrays of a handle that has been used for MPC: [B][N][.]
-    T *x_old, *u_old, *KT_old;
-};
-
-// dst[k] = src[min(k + shift, DIM_N - 1)] (or 0 beyond the data when zero_fill) for k < DIM_N - 1.  dst2 (optional) receives the same values.  When
-// copy_last, knot DIM_N - 1 of src is also copied to dst/dst2 (needed when dst is not src).  The array is walked as ONE flat run in ascending order in
-// pieces of 8 elements per lane: a piece is read completely before it is written and only ever reads at or above what it writes, so shifting in place is
-// safe -- and the loads of a piece are in flight together (one element per lane and knot at a time, as a first version did, spends one memory latency per
-// knot: 0.3 ms of a 1.2 ms control cycle for the two cost-to-go arrays).
-template <typename T>
-PDDP_HD void mpc_shift(const Wave& w, T* dst, T* dst2, const T* src, int per_knot, int DIM_N, int shift, bool zero_fill, bool copy_last) {
-    constexpr int U = 8;
-    const int total = (DIM_N - 1) * per_knot, last = (DIM_N - 1) * per_knot, off = shift * per_knot;
-    for (int base = 0; base < total; base += w.nlanes * U) {
-        T v[U];
-#pragma unroll
-        for (int j = 0; j < U; j++) {
-            const int e = base + j * w.nlanes + w.lane;
-            if (e < total) {
-                const int es = e + off;
-                v[j] = es < last ? src[es] : (zero_fill ? T(0) : src[last + (e % per_knot)]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < U; j++) {
-            const int e = base + j * w.nlanes + w.lane;
-            if (e < total) { dst[e] = v[j]; if (dst2) dst2[e] = v[j]; }
-        }
-    }
-    if (copy_last) PDDP_FOR(i, per_knot) { const T val = src[last + i]; dst[last + i] = val; if (dst2) dst2[last + i] = val; }
-}
 // workgroup-wide stage boundary of the load kernel (its waves share the shifting; one "wave" on the host)
 PDDP_HD void mpc_block_sync(int nwaves) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -68,19 +37,47 @@ struct MpcScratch {
     T x[P::NX], xn[P::NX], u[P::NU], dx[P::NX];
 };
 
-template <typename P, int INTEG, typename T, int V = -1>
+// The previous solution of a problem that lives somewhere else than the problem being loaded (GATHER form: a slot of the handle, read only; the load writes the
+// shifted or cleared arrays into a problem of the intake area).
+template <typename T>
+struct MpcPrev {
+    const T *xb, *u, *d, *KT, *P, *Pp, *p, *pp;      // the slot's own rows: xb both halves
+    int cur;
+};
+template <typename T>
+PDDP_HD MpcPrev<T> mpc_prev_of(const Buffers<T>& hb, const Dims& dm, int NX, int NU, size_t q) {
+    const size_t N = dm.N;
+    return MpcPrev<T>{hb.xb + q * 2 * N * NX, hb.ucur + q * N * NU, hb.dcur + q * N * NX, hb.KT + q * N * NX * NU, hb.P + q * N * NX * NX, hb.Pp + q * N * NX * NX,
+                      hb.p + q * N * NX, hb.pp + q * N * NX, hb.state[q].cur};
+}
+
+// knot N-1 of u / KT, which their shift (DIM_N = N - 1) never reaches: copied by the gathering form only
+template <bool GATHER, typename T>
+PDDP_HD void mpc_gather_last_knot(const Wave& w, T* dst, const T* src, int per, int N) {
+    if constexpr (GATHER) { PDDP_FOR(e, per) dst[(N - 1) * per + e] = src[(N - 1) * per + e]; }
+}
+
+// GATHER (compile time): shift sources are `prev`'s arrays instead of the problem's own.  Shifting in place leaves some regions untouched and so skips them; the gathering
+// form copies them: shift == 0 (in place a no-op for P, p, Pp, pp, d, u, KT), knots N-2 and N-1 of u / KT, knot N-1 of d, P, p, Pp, pp.  (Both halves of xb are
+// written whole in either form.)  With GATHER = false every condition and argument below folds to what the in-place kernel always had.
+template <typename P, int INTEG, typename T, int V = -1, bool GATHER = false>
 PDDP_HD void mpc_load_body(const Wave& w, MpcScratch<P, T>& s, const Buffers<T>& b, const MpcBuffers<T>& mb, const Dims& dm, T dt, int pb,
-                           const T* xActual, int shift, int clear_vars, int full_rollout, int wave_id = 0, int nwaves = 1, float* pipe = nullptr) {
+                           const T* xActual, int shift, int clear_vars, int full_rollout, int wave_id = 0, int nwaves = 1, float* pipe = nullptr,
+                           const MpcPrev<T>* prev = nullptr) {
     // wave_id / nwaves: the workgroup's waves share the shifting and the fall-back copies (task t runs on wave t % nwaves); the rollout is wave 0's
     constexpr int NX = P::NX, NU = P::NU, NM = NX + NU;
     const int N = dm.N;
-    const int cur = b.state[pb].cur;
+    const int cur = GATHER ? prev->cur : b.state[pb].cur;
     T* x0 = b.xb + ((size_t)pb * 2 + 0) * N * NX;          // after the load: the rolled-out trajectory
     T* x1 = b.xb + ((size_t)pb * 2 + 1) * N * NX;          // after the load: the shifted previous trajectory (the reference's d_xp)
-    T* xsrc = cur == 0 ? x0 : x1;
+    const T* xsrc = GATHER ? prev->xb + (size_t)cur * N * NX : (cur == 0 ? x0 : x1);
     T* u = b.ucur + (size_t)pb * N * NU; T* d = b.dcur + (size_t)pb * N * NX;
     T* KT = b.KT + (size_t)pb * N * NX * NU;
     T* Pm = b.P + (size_t)pb * N * NX * NX; T* Pp = b.Pp + (size_t)pb * N * NX * NX; T* pv = b.p + (size_t)pb * N * NX; T* pp = b.pp + (size_t)pb * N * NX;
+    const T *u_s, *d_s, *KT_s, *Pm_s, *Pp_s, *pv_s, *pp_s;      // where the previous solution is read (xsrc above: the current half of xb)
+    if constexpr (GATHER) { u_s = prev->u; d_s = prev->d; KT_s = prev->KT; Pm_s = prev->P; Pp_s = prev->Pp; pv_s = prev->p; pp_s = prev->pp; }
+    else { u_s = u; d_s = d; KT_s = KT; Pm_s = Pm; Pp_s = Pp; pv_s = pv; pp_s = pp; }
+    // (GATHER || shift > 0) below: in place, shift == 0 leaves the arrays as they are
     T* x_old = mb.x_old + (size_t)pb * N * NX; T* u_old = mb.u_old + (size_t)pb * N * NU; T* KT_old = mb.KT_old + (size_t)pb * N * NX * NU;
     bool piped = false;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -103,23 +100,24 @@ PDDP_HD void mpc_load_body(const Wave& w, MpcScratch<P, T>& s, const Buffers<T>&
         }
         if (wave_id == 3) {
             if (clear_vars) { PDDP_FOR(e, N * NX * NX) Pm[e] = 0; PDDP_FOR(e, N * NX) pv[e] = 0; }
-            else if (shift > 0) { mpc_shift<T>(w, Pm, nullptr, Pm, NX * NX, N, shift, false, false); mpc_shift<T>(w, pv, nullptr, pv, NX, N, shift, false, false); }
+            else if (GATHER || shift > 0) { mpc_shift<T>(w, Pm, nullptr, Pm_s, NX * NX, N, shift, false, GATHER); mpc_shift<T>(w, pv, nullptr, pv_s, NX, N, shift, false, GATHER); }
             return;
         }
         if (wave_id == 4) {
             if (clear_vars) { PDDP_FOR(e, N * NX * NX) Pp[e] = 0; PDDP_FOR(e, N * NX) pp[e] = 0; }
-            else if (shift > 0) { mpc_shift<T>(w, Pp, nullptr, Pp, NX * NX, N, shift, false, false); mpc_shift<T>(w, pp, nullptr, pp, NX, N, shift, false, false); }
+            else if (GATHER || shift > 0) { mpc_shift<T>(w, Pp, nullptr, Pp_s, NX * NX, N, shift, false, GATHER); mpc_shift<T>(w, pp, nullptr, pp_s, NX, N, shift, false, GATHER); }
             return;
         }
         if (wave_id == 5) {
             if (clear_vars) { PDDP_FOR(e, N * NX * NU) KT[e] = 0; }
-            else if (shift > 0) mpc_shift<T>(w, KT, nullptr, KT, NX * NU, N - 1, shift, true, false);
+            else if (GATHER || shift > 0) { mpc_shift<T>(w, KT, nullptr, KT_s, NX * NU, N - 1, shift, true, GATHER); mpc_gather_last_knot<GATHER, T>(w, KT, KT_s, NX * NU, N); }
+            if constexpr (GATHER) wsync();                                                    // (the copy below reads what other lanes of this wave have just written)
             mpc_shift<T>(w, KT_old, nullptr, KT, NX * NU, N + 1, 0, false, false);            // plain copy of all N knots, 8 loads in flight per lane
             tl_pipe_post(pl.flag + 7, 1);
             return;
         }
         if (wave_id == 6) {
-            if (shift > 0) mpc_shift<T>(w, d, nullptr, d, NX, N, shift, false, false);
+            if (GATHER || shift > 0) mpc_shift<T>(w, d, nullptr, d_s, NX, N, shift, false, GATHER);
             PDDP_FOR(e, N * NU) b.du[(size_t)pb * N * NU + e] = 0;
             PDDP_FOR(e, dm.A) b.dmax[(size_t)pb * dm.A + e] = 0;
             PDDP_FOR(e, dm.M) b.err[(size_t)pb * dm.M + e] = 0;
@@ -129,7 +127,7 @@ PDDP_HD void mpc_load_body(const Wave& w, MpcScratch<P, T>& s, const Buffers<T>&
         if (wave_id != 0) return;
         mpc_shift<T>(w, cur == 0 ? x0 : x1, cur == 0 ? x1 : x0, xsrc, NX, N, shift, false, true);
         if (clear_vars) { PDDP_FOR(e, N * NU) u[e] = 0; }
-        else if (shift > 0) mpc_shift<T>(w, u, nullptr, u, NU, N - 1, shift, true, false);
+        else if (GATHER || shift > 0) { mpc_shift<T>(w, u, nullptr, u_s, NU, N - 1, shift, true, GATHER); mpc_gather_last_knot<GATHER, T>(w, u, u_s, NU, N); }
         wsync();
         PDDP_FOR(e, N * NU) u_old[e] = u[e];
         PDDP_FOR(e, N * NX) x_old[e] = x1[e];
@@ -168,7 +166,7 @@ PDDP_HD void mpc_load_body(const Wave& w, MpcScratch<P, T>& s, const Buffers<T>&
     const auto mine = [&](int task) { return task % nwaves == wave_id; };
     if (mine(0)) {
         mpc_shift<T>(w, cur == 0 ? x0 : x1, cur == 0 ? x1 : x0, xsrc, NX, N, shift, false, true);
-        if (shift > 0) mpc_shift<T>(w, d, nullptr, d, NX, N, shift, false, false);
+        if (GATHER || shift > 0) mpc_shift<T>(w, d, nullptr, d_s, NX, N, shift, false, GATHER);
         PDDP_FOR(e, N * NU) b.du[(size_t)pb * N * NU + e] = 0;
         PDDP_FOR(e, dm.A) b.dmax[(size_t)pb * dm.A + e] = 0;
         PDDP_FOR(e, dm.M) b.err[(size_t)pb * dm.M + e] = 0;
@@ -178,10 +176,10 @@ PDDP_HD void mpc_load_body(const Wave& w, MpcScratch<P, T>& s, const Buffers<T>&
         if (mine(1)) { PDDP_FOR(e, N * NX * NX) Pm[e] = 0; PDDP_FOR(e, N * NX) pv[e] = 0; }
         if (mine(2)) { PDDP_FOR(e, N * NX * NX) Pp[e] = 0; PDDP_FOR(e, N * NX) pp[e] = 0; }
         if (mine(3)) { PDDP_FOR(e, N * NU) u[e] = 0; PDDP_FOR(e, N * NX * NU) KT[e] = 0; }
-    } else if (shift > 0) {
-        if (mine(1)) { mpc_shift<T>(w, Pm, nullptr, Pm, NX * NX, N, shift, false, false); mpc_shift<T>(w, pv, nullptr, pv, NX, N, shift, false, false); }
-        if (mine(2)) { mpc_shift<T>(w, Pp, nullptr, Pp, NX * NX, N, shift, false, false); mpc_shift<T>(w, pp, nullptr, pp, NX, N, shift, false, false); }
-        if (mine(3)) { mpc_shift<T>(w, u, nullptr, u, NU, N - 1, shift, true, false); mpc_shift<T>(w, KT, nullptr, KT, NX * NU, N - 1, shift, true, false); }
+    } else if (GATHER || shift > 0) {
+        if (mine(1)) { mpc_shift<T>(w, Pm, nullptr, Pm_s, NX * NX, N, shift, false, GATHER); mpc_shift<T>(w, pv, nullptr, pv_s, NX, N, shift, false, GATHER); }
+        if (mine(2)) { mpc_shift<T>(w, Pp, nullptr, Pp_s, NX * NX, N, shift, false, GATHER); mpc_shift<T>(w, pp, nullptr, pp_s, NX, N, shift, false, GATHER); }
+        if (mine(3)) { mpc_shift<T>(w, u, nullptr, u_s, NU, N - 1, shift, true, GATHER); mpc_shift<T>(w, KT, nullptr, KT_s, NX * NU, N - 1, shift, true, GATHER); mpc_gather_last_knot<GATHER, T>(w, u, u_s, NU, N); mpc_gather_last_knot<GATHER, T>(w, KT, KT_s, NX * NU, N); }
     }
     mpc_block_sync(nwaves);
     // the fall-back: shifted previous trajectory / controls / gains (u_old is the reference's d_up: knots N-2, N-1 keep whatever they held).  The controls

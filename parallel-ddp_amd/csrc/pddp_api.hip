@@ -200,6 +200,28 @@ extern "C" int pddp_mpc_load(pddp_handle h, const void* xActual, const void* xGo
     if (!xActual || !xGoal || !shift) return fail(PDDP_EINVAL, "pddp_mpc_load: null argument");
     return s->mpc_load(xActual, xGoal, shift, clear_vars, full_rollout);
 }
+// control cycles of named slots: every argument is checked here, before the handle is touched
+static int mpc_problems_check(SolverBase* s, const char* who, int count, const int* idx, const void* xActual, const void* xGoal, const int* shift) {
+    if (count >= 1 && (!idx || !xActual || !xGoal || !shift)) return fail(PDDP_EINVAL, std::string(who) + ": null idx, xActual, xGoal or shift");
+    if (int rc = slots_check(s, who, count, idx)) return rc;
+    for (int i = 0; i < count; i++)
+        if (shift[i] < 0 || shift[i] >= s->cfg.N - 1) return fail(PDDP_EINVAL, std::string(who) + ": shift[" + std::to_string(i) + "] = " + std::to_string(shift[i]) + " must be in [0, N-2]");
+    return 0;
+}
+extern "C" int pddp_mpc_solve_problems(pddp_handle h, int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout,
+                                       int ifd, int max_iter, double time_budget_ms, int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success,
+                                       int* iters) {
+    IMPL(h);
+    if (int rc = mpc_problems_check(s, "pddp_mpc_solve_problems", count, idx, xActual, xGoal, shift)) return rc;
+    if (max_iter < 1 || max_iter > s->cfg.max_iter) return fail(PDDP_EINVAL, "pddp_mpc_solve_problems: max_iter must be in [1, config.max_iter]");
+    return s->mpc_solve_problems(count, idx, xActual, xGoal, shift, clear_vars, full_rollout, ifd, max_iter, time_budget_ms, poll_every, x, u, KT, Jout, alphaOut, success, iters);
+}
+extern "C" int pddp_mpc_load_problems(pddp_handle h, int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) {
+    IMPL(h);
+    if (int rc = mpc_problems_check(s, "pddp_mpc_load_problems", count, idx, xActual, xGoal, shift)) return rc;
+    return s->mpc_load_problems(count, idx, xActual, xGoal, shift, clear_vars, full_rollout);
+}
+extern "C" int pddp_mpc_slots_profile(pddp_handle h, int timing, float* ms3) { IMPL(h); return s->mpc_slots_profile(timing, ms3); }
 extern "C" int pddp_get_config(pddp_handle h, pddp_config* out) { IMPL(h); if (!out) return fail(PDDP_EINVAL, "null argument"); *out = s->cfg; return 0; }
 extern "C" int pddp_stream(pddp_handle h, void** hip_stream) { IMPL(h); if (!hip_stream) return fail(PDDP_EINVAL, "null argument"); *hip_stream = (void*)s->stream; return 0; }
 

@@ -63,6 +63,12 @@ struct SolverBase {
     virtual int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
                           int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) = 0;
     virtual int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) = 0;   // mpc_solve's load stage alone (teacher-forcing hook)
+    // control cycles of named slots (pddp_mpc_solve_problems / pddp_mpc_load_problems): entry i of the [count] inputs and outputs belongs to slot idx[i]; idx, shift and
+    // max_iter are validated by the caller (pddp_api.hip)
+    virtual int mpc_solve_problems(int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter,
+                                   double budget_ms, int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) = 0;
+    virtual int mpc_load_problems(int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) = 0;
+    virtual int mpc_slots_profile(int on, float* ms3) = 0;      // pddp_mpc_slots_profile (measurement)
     int bench_mode = 0;
     bool h_overridden = false;     // pddp_set_array("H"): the cost Hessian is no longer known to be the plant's own (diagonal for the joint-space cost)
     virtual void drop_graph() = 0;

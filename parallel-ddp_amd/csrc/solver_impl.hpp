@@ -6,6 +6,7 @@
 #include "handle_setup.hpp"
 #include "slots.hpp"
 #include "cost_table.hpp"
+#include "mpc_slots.hpp"
 #include "tl_launch.hpp"
 #include "mx_launch.hpp"
 
@@ -166,6 +167,7 @@ struct Solver : SolverBase {
         if (h_stage) hipHostFree(h_stage);
         if (h_state) hipHostFree(h_state);
         delete intake;
+        for (hipEvent_t e : slots_ev) if (e) hipEventDestroy(e);
         if (d_slot_idx) hipFree(d_slot_idx);
         if (d_slot_stage) hipFree(d_slot_stage);
         if (stream && !intake_of) hipStreamDestroy(stream);        // (an intake area runs on its handle's stream)
@@ -199,6 +201,7 @@ struct Solver : SolverBase {
         if (intake_of) stream = intake_of->stream;
         else HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         dm.N = c.N; dm.M = c.M; dm.A = c.A; dm.NB = c.N / c.M;
+        cap_batch = c.batch;
         nis_tl7_batch = c.batch <= kNisTl7MaxBatch;
         bp_lane_groups = (size_t)c.batch * c.M >= 4096;     // measured crossovers on MI355X (Kuka N=128): wide <= 256 problems < cooperative < 1024 <= lane groups
         bp_wide = (size_t)c.batch * c.M <= 1024 && P::NX >= 12;
@@ -710,15 +713,32 @@ struct Solver : SolverBase {
     int mpc_enqueue_load(const char* who, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) {
         const size_t B = cfg.batch, N = cfg.N;
         for (size_t i = 0; i < B; i++) if (shift[i] < 0 || shift[i] >= (int)N - 1) return fail(PDDP_EINVAL, std::string(who) + ": shift must be in [0, N-2]");
+        if (int rc = mpc_admit(who, clear_vars)) return rc;
+        return mpc_launch_load(xActual, xGoal, shift, clear_vars, full_rollout);
+    }
+    // what a warm start means for the handle as a whole (the named-slot calls take it on the handle, their cycles run on its intake area).  whole = false: the call
+    // clears or shifts the named slots only, so clear_vars = 1 there does not lift the refusal -- the other slots' interior cost-to-go is as stale as before; it stays in
+    // force until pddp_mpc_solve / pddp_mpc_load clears every slot.
+    int mpc_admit(const char* who, int clear_vars, bool whole = true) {
         if (lean_ctg_ran && !clear_vars)
             return fail(PDDP_EINVAL, std::string(who) + ": this handle iterated with boundary_cost_to_go_only = 1, so its interior cost-to-go slots are stale and a warm start "
-                                     "(clear_vars = 0) would shift them into the block boundaries; call with clear_vars = 1 once, or create the handle without that option");
-        lean_ctg_ran = false;
+                                     "(clear_vars = 0) would shift them into the block boundaries; call with clear_vars = 1 once, or create the handle without that option" +
+                                     (whole ? "" : " (named slots: clear_vars = 1 clears the named slots only and is accepted, but the refusal stays in force for every slot "
+                                                   "until pddp_mpc_solve or pddp_mpc_load with clear_vars = 1 has cleared the whole handle)"));
+        if (whole) lean_ctg_ran = false;
         if (!mpc_used) { mpc_used = true; drop_graph(); }
+        return 0;
+    }
+    size_t cap_batch = 0;      // problems the handle's buffers were allocated for (an intake area's cfg.batch is the chunk in flight, <= this)
+    // inputs of cfg.batch problems -> device, then the k_mpc_load launch.  from: the previous solutions are read from slots d_idx[i] of another handle's buffers
+    // (k_mpc_load_slots: an intake area loading named slots of its handle); the kernel form is selected the same way for both.
+    int mpc_launch_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, const Buffers<T>* from = nullptr,
+                        const int* d_idx = nullptr, int from_batch = 0) {
+        const size_t B = cfg.batch, Bc = cap_batch, N = cfg.N;
         // one pinned staging area: pageable host memory would make every small transfer of the cycle a synchronous staging copy of its own
         const size_t out_stride = (size_t)cfg.max_iter + 2;
-        const size_t o_state = 0, o_xb = o_state + B * sizeof(SolverState<T>), o_u = o_xb + B * 2 * N * NX * sizeof(T), o_KT = o_u + B * N * NU * sizeof(T),
-                     o_J = o_KT + B * N * NX * NU * sizeof(T), o_a = o_J + B * out_stride * sizeof(T), need_bytes = o_a + B * out_stride * sizeof(int) + 16 * B;
+        const size_t o_state = 0, o_xb = o_state + Bc * sizeof(SolverState<T>), o_u = o_xb + Bc * 2 * N * NX * sizeof(T), o_KT = o_u + Bc * N * NU * sizeof(T),
+                     o_J = o_KT + Bc * N * NX * NU * sizeof(T), o_a = o_J + Bc * out_stride * sizeof(T), need_bytes = o_a + Bc * out_stride * sizeof(int) + 16 * Bc;
         if (h_stage_bytes < need_bytes) {
             if (h_stage) hipHostFree(h_stage);
             h_stage = nullptr; h_stage_bytes = 0;
@@ -729,18 +749,29 @@ struct Solver : SolverBase {
             unsigned char* hi = h_stage;                            // inputs first (the outputs overwrite them after the solve)
             T* hx = (T*)hi; T* hg = hx + B * NX; int* hs = (int*)(hg + B * NX);
             std::memcpy(hx, xActual, B * NX * sizeof(T)); std::memcpy(hg, xGoal, B * NX * sizeof(T)); std::memcpy(hs, shift, B * sizeof(int));
-            HIPCHK(hipMemcpyAsync(d_xActual, hx, 2 * B * NX * sizeof(T) + B * sizeof(int), hipMemcpyHostToDevice, stream));   // the load kernel moves goals / shifts where the sweeps read them
+            if (B == Bc) HIPCHK(hipMemcpyAsync(d_xActual, hx, 2 * B * NX * sizeof(T) + B * sizeof(int), hipMemcpyHostToDevice, stream));   // the load kernel moves goals / shifts where the sweeps read them
+            else {                                                  // a chunk smaller than the intake area: the three runs lie apart on the device
+                HIPCHK(hipMemcpyAsync(d_xActual, hx, B * NX * sizeof(T), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(d_goal_in, hg, B * NX * sizeof(T), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(d_shift, hs, B * sizeof(int), hipMemcpyHostToDevice, stream));
+            }
         }
         bool split_roll = false;
+        const int tsm = (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0;
         if constexpr (P::PLANT == 4 && INTEG == 1 && sizeof(T) == 4) {                // float arm with a built-in robot model: the warm-start rollout split over two waves
             const char* fpenv = ksel_fp(cfg);
             if (tl_variant >= 0 && !(fpenv && (std::string(fpenv) == "lg" || std::string(fpenv) == "coop"))) {
                 split_roll = true;
-                if (tl_variant == 0) hipLaunchKernelGGL((k_mpc_load<P, INTEG, T, 0>), dim3(B), dim3(512), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
+                if (from) {
+                    if (tl_variant == 0) hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T, 0>), dim3(B), dim3(512), 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
+                    else hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T, 1>), dim3(B), dim3(512), 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
+                }
+                else if (tl_variant == 0) hipLaunchKernelGGL((k_mpc_load<P, INTEG, T, 0>), dim3(B), dim3(512), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
                 else hipLaunchKernelGGL((k_mpc_load<P, INTEG, T, 1>), dim3(B), dim3(512), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
             }
         }
-        if (!split_roll) hipLaunchKernelGGL((k_mpc_load<P, INTEG, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
+        if (!split_roll && from) hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T>), dim3(B), dim3(256), 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
+        else if (!split_roll) hipLaunchKernelGGL((k_mpc_load<P, INTEG, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
         return 0;
     }
     int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) override {
@@ -751,10 +782,18 @@ struct Solver : SolverBase {
     }
     int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
                   int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) override {
-        const size_t B = cfg.batch, N = cfg.N;
         if (max_iter < 1 || max_iter > cfg.max_iter) return fail(PDDP_EINVAL, "mpc_solve: max_iter must be in [1, config.max_iter]");
         const double t0 = now_ms();
         if (int rc = mpc_enqueue_load("mpc_solve", xActual, xGoal, shift, clear_vars, full_rollout)) return rc;
+        return mpc_cycle(t0, ifd, max_iter, budget_ms, poll_every, x, u, KT, Jout, alphaOut, success, iters, [] {});
+    }
+    // A control cycle behind its load stage, for the cfg.batch problems of this handle (pddp_mpc_solve: the whole handle; pddp_mpc_solve_problems: a chunk of named slots
+    // on the intake area): initial cost and setup with alphaIndex kept, the iLQR loop under this call's iteration limit and time budget (t0: the start of the call),
+    // fall-back and result records.  after_store() runs behind every k_mpc_store launch, before the wait: what the caller enqueues there rides the same synchronisation.
+    template <typename AfterStore>
+    int mpc_cycle(double t0, int ifd, int max_iter, double budget_ms, int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters,
+                  AfterStore&& after_store) {
+        const size_t B = cfg.batch, N = cfg.N;
         const size_t out_stride = (size_t)cfg.max_iter + 2;
         const size_t rec_state = (sizeof(SolverState<T>) + 15) / 16 * 16;
         const size_t rec_bytes = (rec_state + (N * NX + N * NU + N * NX * NU + out_stride) * sizeof(T) + out_stride * sizeof(int) + 15) / 16 * 16;   // <= the six separate areas' share per problem
@@ -771,9 +810,10 @@ struct Solver : SolverBase {
             if ((rc = iterate(max_iter))) { sp.max_iter = saved_max_iter; return rc; }
             sp.max_iter = saved_max_iter;
             // k_mpc_store also packs every problem's results (state | x | u | K | J | step sizes) into one device run: ONE transfer back instead of six
-            if (!d_mpc_out) { int arc = alloc("mpc_out", &d_mpc_out, B * rec_bytes); if (arc) return arc; }
+            if (!d_mpc_out) { int arc = alloc("mpc_out", &d_mpc_out, cap_batch * rec_bytes); if (arc) return arc; }
             hipLaunchKernelGGL((k_mpc_store<P, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, 1, d_mpc_out, (int)rec_bytes, (int)out_stride);
             HIPCHK(hipGetLastError());
+            after_store();
             HIPCHK(hipMemcpyAsync(h_stage, d_mpc_out, B * rec_bytes, hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
             hstate.resize(B);
@@ -812,6 +852,7 @@ struct Solver : SolverBase {
         if (rc) return rc;
         hipLaunchKernelGGL((k_mpc_store<P, T>), dim3(B), dim3(64), 0, stream, b, mb, dm, 0, (unsigned char*)nullptr, 0, 0);   // copies only: the states status() fetched above stay valid
         HIPCHK(hipGetLastError());
+        after_store();
         if ((rc = store_impl(x, u, KT, Jout, alphaOut, nullptr, fresh))) return rc;
         for (size_t i = 0; i < B; i++) { if (success) success[i] = hstate[i].took_step; if (iters) iters[i] = hstate[i].iter; }
         return 0;
@@ -820,7 +861,7 @@ struct Solver : SolverBase {
     int status(int* done, int* iters) override {
         hstate.resize(cfg.batch);
         const size_t bytes = cfg.batch * sizeof(SolverState<T>);
-        if (!h_state) HIPCHK(hipHostMalloc((void**)&h_state, bytes, hipHostMallocDefault));   // pinned: the poll is one asynchronous copy + one wait
+        if (!h_state) HIPCHK(hipHostMalloc((void**)&h_state, cap_batch * sizeof(SolverState<T>), hipHostMallocDefault));   // pinned: the poll is one asynchronous copy + one wait
         HIPCHK(hipMemcpyAsync(h_state, b.state, bytes, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         std::memcpy(hstate.data(), h_state, bytes);
@@ -851,7 +892,8 @@ struct Solver : SolverBase {
     // ---- individual slots of a loaded handle between sweeps: pddp_load_problems / pddp_store_problems (slots.hpp)
     // The intake area: a second Solver of the same type for min(batch, kSlotIntakeMax) problems on this handle's stream, with this handle's RESOLVED kernel selection
     // (adopt_selection: the choices init() derives from the batch size are the handle's, not those of a 256-problem handle), created at the first refill.  load() of the
-    // intake is the handle's own init path -- the same kernel families, the same bits; only the init-mode launches ever run on it.
+    // intake is the handle's own init path -- the same kernel families, the same bits.  Control cycles of named slots run sweeps on the same area (mpc_problems below), so
+    // a refill does not rely on what the area holds: load_problems clears the solver states and the Jout / alphaOut rows of its chunk first.
     Solver* intake = nullptr;
     const Solver* intake_of = nullptr;             // set on the intake itself: the handle it serves
     int* d_slot_idx = nullptr;                     // [kSlotIntakeMax] the slot indices of the chunk in flight
@@ -903,7 +945,7 @@ struct Solver : SolverBase {
         copy(ib.xb, b.xb, 2 * N * NX * e, 2 * N * NX * e, N * NX * e);            // half 0: the fresh state's cur
         same(ib.ucur, b.ucur, N * NU * e); same(ib.xGoal, b.xGoal, NX * e);
         same(ib.state, b.state, sizeof(SolverState<T>));
-        same(ib.Jout, b.Jout, out * e); same(ib.alphaOut, b.alphaOut, out * sizeof(int));      // (the intake's rows are zero behind element 0: no sweep ever runs there)
+        same(ib.Jout, b.Jout, out * e); same(ib.alphaOut, b.alphaOut, out * sizeof(int));      // (the intake's rows are zero behind element 0: load_problems clears them in front of the init path, which writes element 0)
         if (b.ABc) ok = ok && slot_add_abc(t, ib.ABc, b.ABc, cfg.N, e); else same(ib.AB, b.AB, N * NX * NM * e);
         same(ib.H, b.H, N * NM * NM * e); same(ib.g, b.g, N * NM * e);
         if (b.Hc) same(ib.Hc, b.Hc, N * 49 * e);
@@ -932,6 +974,10 @@ struct Solver : SolverBase {
             in.cfg.batch = n;                                        // this chunk's view of the intake area: launches and transfers cover n problems
             if (hipMemcpyAsync(d_slot_idx, idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, "pddp_load_problems: index transfer failed"); break; }
             if (fetch.n) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, fetch.n), dim3(256), 0, stream, fetch, (const int*)d_slot_idx, n, (int)cfg.batch, 1);
+            // what the init path keeps or does not write, as on a fresh handle whatever ran on the intake before (a control cycle of named slots leaves some robot's
+            // state and observables there): state.pw = 0, the rows of Jout / alphaOut zero behind element 0
+            if (hipMemsetAsync(in.b.state, 0, (size_t)n * sizeof(SolverState<T>), stream) != hipSuccess || hipMemsetAsync(in.b.Jout, 0, (size_t)n * (cfg.max_iter + 2) * sizeof(T), stream) != hipSuccess ||
+                hipMemsetAsync(in.b.alphaOut, 0, (size_t)n * (cfg.max_iter + 2) * sizeof(int), stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, "pddp_load_problems: clearing the intake area failed"); break; }
             rc = in.enqueue_load((const T*)x0 + (size_t)c0 * N * NX, (const T*)u0 + (size_t)c0 * N * NU, (const T*)xg + (size_t)c0 * NX, nullptr, nullptr, nullptr, nullptr, 0, 1,
                                  ignore_first_defect);
             if (!rc) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, tab.n), dim3(256), 0, stream, tab, (const int*)d_slot_idx, n, (int)cfg.batch, 0);
@@ -976,6 +1022,82 @@ struct Solver : SolverBase {
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
+    }
+    // ---- control cycles of named slots: pddp_mpc_solve_problems / pddp_mpc_load_problems (DESIGN.md "control cycles of named slots")
+    // The intake area is where the cycle runs: per chunk of up to slot_chunk() named slots their whole persistent state goes in (k_slots_scatter, to_compact = 1), the
+    // intake runs the load stage and the cycle it would run as a handle of n problems (mpc_launch_load, mpc_cycle: the code pddp_mpc_solve runs), and every array goes
+    // back to its slot (to_compact = 0).  No kernel of a sweep learns to skip problems; an unnamed slot is never an operand of anything.
+    // what travels in and out per slot: mpc_slots.hpp
+    bool cycle_tables(std::vector<SlotTable>& in_t, std::vector<SlotTable>& out_t) {
+        const Solver& in = *intake;
+        const MpcSlotSide<T> is{b.cwt ? in.d_cwt : nullptr, in.d_xActual, in.d_goal_in, in.d_shift}, hs{b.cwt ? d_cwt : nullptr, d_xActual, d_goal_in, d_shift};
+        return mpc_slot_tables<NX, NU, T>(in_t, out_t, in.b, in.mb, is, b, mb, hs, cfg.N, cfg.M, cfg.A, cfg.max_iter, cfg.ee_cost);
+    }
+    // pddp_mpc_slots_profile (measurement): HIP events around the in stage (movers + load kernel), the cycle and the out stage of every chunk
+    bool slots_timing = false;
+    hipEvent_t slots_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float slots_ms[3] = {0.f, 0.f, 0.f};
+    int mpc_slots_profile(int on, float* ms3) override {
+        if (on >= 0) {
+            if (on && !slots_ev[0]) for (hipEvent_t& e : slots_ev) HIPCHK(hipEventCreate(&e));
+            slots_timing = on != 0;
+        }
+        if (ms3) for (int k = 0; k < 3; k++) ms3[k] = slots_ms[k];
+        return 0;
+    }
+    // solve = false: the load stage alone (pddp_mpc_load_problems), results left in the slots
+    int mpc_problems(bool solve, int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter,
+                     double budget_ms, int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) {
+        const double t0 = now_ms();                                  // the time budget runs from the start of the call, whatever the number of chunks
+        const char* who = solve ? "pddp_mpc_solve_problems" : "pddp_mpc_load_problems";
+        if (lean_ctg_ran && !clear_vars) return mpc_admit(who, clear_vars, false);      // (refused before the intake area is touched)
+        if (int rc = ensure_intake()) return rc;
+        if (int rc = mpc_admit(who, clear_vars, false)) return rc;
+        Solver& in = *intake;
+        in.mpc_used = true; in.lean_ctg_ran = false; in.bench_mode = bench_mode; in.cfg.ee_cost_shift = cfg.ee_cost_shift;
+        slots_ms[0] = slots_ms[1] = slots_ms[2] = 0.f;
+        std::vector<SlotTable> in_t, out_t;
+        if (!cycle_tables(in_t, out_t)) return fail(PDDP_EINVAL, std::string(who) + ": internal error (slot table)");
+        const size_t N = cfg.N, out = (size_t)cfg.max_iter + 2;
+        const int C = slot_chunk();
+        int rc = 0;
+        for (int c0 = 0; c0 < count && !rc; c0 += C) {
+            const int n = count - c0 < C ? count - c0 : C;
+            in.cfg.batch = n;                                        // this chunk's view of the intake area, as in load_problems
+            if (hipMemcpyAsync(d_slot_idx, idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, std::string(who) + ": index transfer failed"); break; }
+            if (slots_timing) hipEventRecord(slots_ev[0], stream);
+            for (const SlotTable& t : in_t) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)d_slot_idx, n, (int)cfg.batch, 1);
+            if ((rc = in.mpc_launch_load((const T*)xActual + (size_t)c0 * NX, (const T*)xGoal + (size_t)c0 * NX, shift + c0, clear_vars, full_rollout, &b,
+                                         d_slot_idx, (int)cfg.batch))) break;
+            if (slots_timing) hipEventRecord(slots_ev[1], stream);
+            const auto scatter_out = [&] {
+                if (slots_timing) hipEventRecord(slots_ev[2], stream);
+                for (const SlotTable& t : out_t) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)d_slot_idx, n, (int)cfg.batch, 0);
+                if (slots_timing) hipEventRecord(slots_ev[3], stream);
+            };
+            if (solve) {
+                rc = in.mpc_cycle(t0, ifd, max_iter, budget_ms, poll_every, x ? (T*)x + (size_t)c0 * N * NX : nullptr, u ? (T*)u + (size_t)c0 * N * NU : nullptr,
+                                  KT ? (T*)KT + (size_t)c0 * N * NX * NU : nullptr, Jout ? (T*)Jout + (size_t)c0 * out : nullptr, alphaOut ? alphaOut + (size_t)c0 * out : nullptr,
+                                  success ? success + c0 : nullptr, iters ? iters + c0 : nullptr, scatter_out);
+            } else {
+                scatter_out();
+                if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) rc = fail(PDDP_ENODEVICE, "pddp_mpc_load_problems: the load stage failed on the device");
+            }
+            if (slots_timing && !rc && hipEventSynchronize(slots_ev[3]) == hipSuccess)
+                for (int k = 0; k < 3; k++) { float t = 0; if (hipEventElapsedTime(&t, slots_ev[k], slots_ev[k + 1]) == hipSuccess) slots_ms[k] += t; }
+        }
+        in.cfg.batch = C;
+        if (rc) { hipStreamSynchronize(stream); return rc; }
+        if (solve) { note_sweeps_enqueued(); note_setup_weights(); }      // the named slots hold what sweeps left: the handle's lazily rebuilt views are as stale as after pddp_mpc_solve
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    int mpc_solve_problems(int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter,
+                           double budget_ms, int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) override {
+        return mpc_problems(true, count, idx, xActual, xGoal, shift, clear_vars, full_rollout, ifd, max_iter, budget_ms, poll_every, x, u, KT, Jout, alphaOut, success, iters);
+    }
+    int mpc_load_problems(int count, const int* idx, const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) override {
+        return mpc_problems(false, count, idx, xActual, xGoal, shift, clear_vars, full_rollout, 0, 1, 0.0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     }
     int time_sweeps(int sweeps, float* ms_total, float* ms_phase) override {
         HIPCHK(hipStreamSynchronize(stream));

@@ -465,7 +465,7 @@ class Solver:
 
     # ---- teacher-forced hooks
     def _adtype(self, name):
-        return np.int32 if name in ("err", "alphaOut", "tshift", "shift") else self.dtype
+        return np.int32 if name in ("err", "alphaOut", "tshift", "shift", "parts_fresh") else self.dtype
 
     def get(self, name):
         nb = C.c_size_t(0)
@@ -514,6 +514,40 @@ class Solver:
         shift = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.int32), (self.cfg.batch,)))
         self.lib.pddp_mpc_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         self._chk(self.lib.pddp_mpc_load(self.h, _p(xActual), _p(xGoal), _p(shift), int(clear_vars), int(full_rollout)))
+
+    def _slot_inputs(self, idx, xActual, xGoal, shift):
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        xActual, xGoal = self.arr(xActual), self.arr(xGoal)
+        shift = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, np.int32), (idx.size,)))
+        assert xActual.size == idx.size * self.n and xGoal.size == idx.size * self.n
+        return idx, xActual, xGoal, shift
+
+    def mpc_solve_problems(self, idx, xActual, xGoal, shift, clear_vars=0, full_rollout=1, ignore_first_defect=1, max_iter=None, time_budget_ms=0.0, poll_every=4):
+        """pddp_mpc_solve_problems: one control cycle for the slots idx of a loaded handle (entry i of xActual [count][n], xGoal [count][n], shift [count] -> slot idx[i]),
+        warm-started from the solution each slot holds; every other slot keeps what it has.  Returns mpc_solve's dictionary with [count] rows."""
+        idx, xActual, xGoal, shift = self._slot_inputs(idx, xActual, xGoal, shift)
+        K, N, n, m, mi = idx.size, self.cfg.N, self.n, self.m, self.cfg.max_iter
+        out = dict(x=np.zeros((K, N, n), self.dtype), u=np.zeros((K, N, m), self.dtype), KT=np.zeros((K, N, m, n), self.dtype),
+                   Jout=np.zeros((K, mi + 2), self.dtype), alphaOut=np.zeros((K, mi + 2), np.int32), success=np.zeros(K, np.int32), iters=np.zeros(K, np.int32))
+        self.lib.pddp_mpc_solve_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 7
+        self._chk(self.lib.pddp_mpc_solve_problems(self.h, K, _p(idx), _p(xActual), _p(xGoal), _p(shift), int(clear_vars), int(full_rollout), int(ignore_first_defect),
+                                                   int(max_iter if max_iter is not None else mi), float(time_budget_ms), int(poll_every),
+                                                   _p(out["x"]), _p(out["u"]), _p(out["KT"]), _p(out["Jout"]), _p(out["alphaOut"]), _p(out["success"]), _p(out["iters"])))
+        return out
+
+    def mpc_load_problems(self, idx, xActual, xGoal, shift, clear_vars=0, full_rollout=1):
+        """pddp_mpc_load_problems: the load stage of mpc_solve_problems alone for the slots idx; read what it leaves in the slots with get()."""
+        idx, xActual, xGoal, shift = self._slot_inputs(idx, xActual, xGoal, shift)
+        self.lib.pddp_mpc_load_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.pddp_mpc_load_problems(self.h, idx.size, _p(idx), _p(xActual), _p(xGoal), _p(shift), int(clear_vars), int(full_rollout)))
+
+    def mpc_slots_profile(self, timing=-1):
+        """pddp_mpc_slots_profile: stage timing of the following mpc_*_problems calls on (1) / off (0) / as it is (-1); returns the last timed call's [in, cycle, out]
+        stream times in ms."""
+        ms = np.zeros(3, np.float32)
+        self.lib.pddp_mpc_slots_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(self.lib.pddp_mpc_slots_profile(self.h, int(timing), _p(ms)))
+        return ms
 
     def plant_eval_paths(self):
         """`what` codes of pddp_plant_eval per plant function: every implementation of the plant the library carries."""
