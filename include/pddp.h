@@ -220,8 +220,8 @@ int pddp_set_cost_ee(pddp_handle h, double Q_EE1, double Q_EE2, double QF_EE1, d
 int pddp_set_ee_cost_shift(pddp_handle h, int on);
 /* New joint-space cost weights for the following loads / solves (the reference passes Q1, Q2, R, QF1, QF2 on every call,
  * DDPWrappers.cuh:17-21, MPCHelpers.cuh:862-866 through costParams).  Takes effect at the next pddp_load / pddp_solve / pddp_mpc_solve:
- * the cost gradient and Hessian of the current trajectory are rebuilt there.  Arm plant only (the other plants' weights are
- * constants of plants/cost_{pend,cart,quad}.cuh). */
+ * the cost gradient and Hessian of the current trajectory are rebuilt there.  Arm plant only (the other plants' weights default to
+ * the constants of plants/cost_{pend,cart,quad}.cuh and are set with pddp_set_diag_cost / pddp_set_diag_cost_problems below). */
 int pddp_set_cost(pddp_handle h, double Q1, double Q2, double R, double QF1, double QF2);
 /* Cost weights per problem (arm plant).  The record is the handle's cost family's own, in the argument order of the handle-wide call:
  *   joint-space cost (ee_cost = 0): 5 doubles  Q1 Q2 R QF1 QF2                                        (pddp_set_cost)
@@ -243,6 +243,27 @@ int pddp_set_cost(pddp_handle h, double Q1, double Q2, double R, double QF1, dou
 int pddp_cost_record_size(pddp_handle h);
 int pddp_set_cost_problems(pddp_handle h, int count, const int* idx, const double* w /* [count][record] */);
 int pddp_get_cost_problems(pddp_handle h, int count, const int* idx, double* w /* [count][record] */);
+/* Run-time diagonal cost weights of the pendulum, cart-pole and quadrotor (plants 1-3), handle-wide or per problem.  The record is the
+ * diagonal of the cost, 2 n + m doubles (pendulum 5, cart-pole 9, quadrotor 28):
+ *   [ q_0..q_{n-1} | r_0..r_{m-1} | qf_0..qf_{n-1} ]
+ * running knots: H_k = diag(q, r), g_k = [q .* (x_k - xGoal); r .* u_k], cost 1/2 (sum q_i d_i^2 + sum r_j u_j^2); final knot:
+ * H = diag(qf, 0), g = [qf .* d; 0], cost 1/2 sum qf_i d_i^2.  The built-in record is the plant's constants (plants/cost_{pend,cart,quad}.cuh:
+ * q_i = QR(i), r_j = R, qf_i = QF); pddp_get_diag_cost_problems returns it, rounded once to the handle's element type and widened
+ * back, until the first setter call.
+ * Semantics are those of pddp_set_cost_problems: records are in force for the following loads and solves; H, g and the cost of a
+ * trajectory already in a slot are NOT rebuilt by the call; problems that are not named keep theirs and running problems in other slots
+ * are untouched.  The first call of either setter gives the handle a device table [batch][record] in its element type, every row the
+ * built-in record, and drops the captured sweep graph once; later calls only write rows (on the solver's stream, one synchronisation
+ * before the call returns).  pddp_set_diag_cost overwrites every row.  A handle that never calls a setter launches exactly the kernels
+ * and arguments it launches without these entry points.  pddp_load_problems / pddp_mpc_solve_problems / pddp_mpc_load_problems run the
+ * named slots with their own rows.
+ * PDDP_EINVAL, with the handle unchanged: plants 4 and 5; count < 1; a NULL idx or w; an index outside [0, batch); an index named twice;
+ * (setters) a weight that is not finite or is negative, as a double or rounded to the element type; a control weight r_j that is not
+ * > 0 (Quu = R + B' P B has to stay invertible at rho = 0; q and qf may be 0).  The handle need not be loaded yet. */
+int pddp_diag_cost_size(pddp_handle h);
+int pddp_set_diag_cost(pddp_handle h, const double* w /* [record] */);
+int pddp_set_diag_cost_problems(pddp_handle h, int count, const int* idx, const double* w /* [count][record] */);
+int pddp_get_diag_cost_problems(pddp_handle h, int count, const int* idx, double* w /* [count][record] */);
 /* ---- the lock-step experiment around the solver ------------------------- */
 /* simulateForward<T, SUBSTEPS> (examples/WAFR_MPC_examples.cu:111-139): the simulated robot of the lock-step MPC experiment.  Starting
  * from xActual at plant time t0_us (the plan's t0), integrates the plant IN DOUBLE for elapsed_us in `substeps` steps under the trajectory

@@ -98,8 +98,8 @@ PDDP_HD void ls_body(const Buffers<T>& b, const Dims& dm, const SolverParams& sp
 //   rejected: trajectory and derivatives are unchanged (the reference recomputes identical values);
 //   (the reference's P -> Pp, p -> pp copies are a flip of state.pw in the line-search kernel)
 // mode 1 = initAlgGPU derivatives (no copies).
-template <typename P, int INTEG, typename T>
-PDDP_HD void nis_body(const Wave& w, NisScratch<P, INTEG, T>& s, const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw, T dt,
+template <typename P, int INTEG, typename T, typename CW = CostWeights<T>>
+PDDP_HD void nis_body(const Wave& w, NisScratch<P, INTEG, T>& s, const Buffers<T>& b, const Dims& dm, const CW& cw, T dt,
                       int mode, int k, int pb) {
     constexpr int NX = P::NX, NU = P::NU, NM = NX + NU;
     const int N = dm.N;
@@ -137,8 +137,8 @@ PDDP_HD void nis_body(const Wave& w, NisScratch<P, INTEG, T>& s, const Buffers<T
 // the previous solve on these buffers ended with.  The reference reads the initial cost from d_JT[*alphaIndex] (:392) although
 // costKern<T,1> leaves the sum in d_JT[0] and the cost of KNOT a in d_JT[a]: an MPC solve (which keeps *alphaIndex, MPCHelpers.cuh)
 // that follows a solve ending with alphaIndex = a > 0 therefore starts from prevJ = cost of knot a.  Kept, sic.
-template <typename P, typename T>
-PDDP_HD void init_cost_body(const Wave& w, T* cost_k, const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw,
+template <typename P, typename T, typename CW = CostWeights<T>>
+PDDP_HD void init_cost_body(const Wave& w, T* cost_k, const Buffers<T>& b, const Dims& dm, const CW& cw,
                             const SolverParams& sp, int ignore_first_defect, int rollout, int pb, int stage = 0, int keep_alpha = 0) {
     constexpr int NX = P::NX, NU = P::NU;
     const int N = dm.N;

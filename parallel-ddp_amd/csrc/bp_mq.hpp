@@ -113,7 +113,7 @@ __device__ void mq_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, const C
     const T* xc = b.xb + ((size_t)pb * 2 + st.cur) * N * NX; const T* xp2 = b.xb + ((size_t)pb * 2 + st.cur2) * N * NX;
     T* ldsU = lds; T* ldsA = lds + 16; T* ldsI = lds + 32; T* ldsL = lds + 48;
     // the running knots' cost Hessian: diag(weight) -- this lane's state column's entry and its lane group's control's
-    const T wx = cx ? P::weight(cw, sc, 0, N) : T(0), wu = P::weight(cw, NX + g, 0, N);
+    const T wx = cx ? knot_weight<P, T>(b, cw, pb, sc, 0, N) : T(0), wu = knot_weight<P, T>(b, cw, pb, NX + g, 0, N);      // (a DiagTab plant: from the problem's row, once, in front of the knot loop)
     const mx4 zero = {T(0), T(0), T(0), T(0)};
 
     int ks = NBk * (blk + 1) - 1, iterCount;

@@ -86,9 +86,9 @@ PDDP_HD void rollout_seed_from_candidate(const Wave& w, const Dims& dm, const Fp
 // Nonlinear rollout of segment bInd.  Start state: a.segx[bInd] (from the sweep), or xcur[0] for segment 0.
 // Writes x[k+1], u[k] for the segment's knots and the boundary defect.  cost_k (optional, LDS [N]) receives the
 // per-knot cost of every knot this segment owns.
-template <typename P, int INTEG, typename T>
+template <typename P, int INTEG, typename T, typename CW = CostWeights<T>>      // CW: the record as the plant's cost routines take it (plants.hpp DiagCostWeights for a DiagTab plant)
 PDDP_HD void forward_sim_segment(const Wave& w, SimScratch<P, T>& s, const Dims& dm, const FpArgs<T>& a, int bInd,
-                                 const CostWeights<T>& cw, const T* xg, T* cost_k) {
+                                 const CW& cw, const T* xg, T* cost_k) {
     constexpr int NX = P::NX, NU = P::NU;
     const int NBk = dm.NB, kStart = bInd * NBk;
     bool ee = false;

@@ -74,7 +74,10 @@ __global__ void k_fp(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int init_ro
         __syncthreads();
     }
     P::load_model(w, sim.plant, reinterpret_cast<const typename P::Model*>(b.model));
-    forward_sim_segment<P, INTEG, T>(w, sim, dm, a, wave_id, cw, b.xGoal + (size_t)pb * P::NX, cost_k);
+    if constexpr (IsDiagTab<P>::value) {                               // the problem's own diagonal (pb is blockIdx.y: a uniform row, scalar loads)
+        const DiagCostWeights<T> own = diag_cost_weights(cw, b.cwt + (size_t)pb * P::REC);
+        forward_sim_segment<P, INTEG, T>(w, sim, dm, a, wave_id, own, b.xGoal + (size_t)pb * P::NX, cost_k);
+    } else forward_sim_segment<P, INTEG, T>(w, sim, dm, a, wave_id, cw, b.xGoal + (size_t)pb * P::NX, cost_k);
     __syncthreads();
     bool ee = false;
     if constexpr (P::PLANT == 4) ee = cw.ee != 0;
@@ -216,6 +219,9 @@ __global__ __launch_bounds__(64) void k_nis(Buffers<T> b, Dims dm, CostWeights<T
         own = cost_weights_at(b, cw, (int)blockIdx.y);                                // the problem's own weights (uniform: scalar loads)
         wsync();
         nis_body<P, INTEG, T>(this_wave(), s, b, dm, own, dt, mode, blockIdx.x, blockIdx.y);
+    } else if constexpr (IsDiagTab<P>::value) {                        // run-time diagonal of a closed-form plant: the row's address rides behind the record (plants.hpp)
+        const DiagCostWeights<T> own = diag_cost_weights(cw, b.cwt + (size_t)blockIdx.y * P::REC);
+        nis_body<P, INTEG, T>(this_wave(), s, b, dm, own, dt, mode, blockIdx.x, blockIdx.y);
     } else nis_body<P, INTEG, T>(this_wave(), s, b, dm, cw, dt, mode, blockIdx.x, blockIdx.y);
 }
 
@@ -250,7 +256,12 @@ __global__ __launch_bounds__(64) void k_fp_ts(Buffers<T> b, Dims dm, CostWeights
     if (no_sweep) { for (int bInd = 0; bInd < dm.M; bInd++) rollout_seed_from_candidate<P, T>(w, dm, a, bInd); }
     else if (dm.M > 1) forward_sweep<P, T>(w, sw, dm, a);
     P::load_model(w, sim.plant, reinterpret_cast<const typename P::Model*>(b.model));
-    for (int bInd = 0; bInd < dm.M; bInd++) forward_sim_segment<P, INTEG, T>(w, sim, dm, a, bInd, cw, b.xGoal + (size_t)pb * P::NX, cost_k);
+    if constexpr (IsDiagTab<P>::value) {                               // this thread's problem's row: every weight is read where a knot's cost uses it
+        const DiagCostWeights<T> own = diag_cost_weights(cw, b.cwt + (size_t)pb * P::REC);
+        for (int bInd = 0; bInd < dm.M; bInd++) forward_sim_segment<P, INTEG, T>(w, sim, dm, a, bInd, own, b.xGoal + (size_t)pb * P::NX, cost_k);
+    } else {
+        for (int bInd = 0; bInd < dm.M; bInd++) forward_sim_segment<P, INTEG, T>(w, sim, dm, a, bInd, cw, b.xGoal + (size_t)pb * P::NX, cost_k);
+    }
     fp_reduce<T>(w, b, dm, pb, a_idx, cost_k, dnorm, nullptr);
 }
 #define PDDP_UNROLL _Pragma("unroll")
@@ -386,8 +397,8 @@ __device__ __forceinline__ void cf_integrator_step(T* xn, const T* x, const T* u
 // PART 0: the linear sweep alone (k_sweep_cf), PART 1: the rollouts alone (k_fp_cf).  Until round 5 one kernel ran both loops; the register allocation of the two together
 // is what kept it at two waves per SIMD -- asked for three or four, the compiler spilled inside the SWEEP loop (the rollout loop fits 128 registers) -- so they are two
 // launches now, each with its own occupancy; the sweep leaves the segments' start states in the candidates' records, where the rollouts read them as before.
-template <typename P, int INTEG, typename T, int A, int PART>
-__device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s)[P::NX], Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw, T dt, int batch) {
+template <typename P, int INTEG, typename T, int A, int PART, typename CW = CostWeights<T>>      // CW: the record as the plant's cost routines take it (plants.hpp DiagCostWeights for a DiagTab plant)
+__device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s)[P::NX], Buffers<T>& b, const Dims& dm, const CW& cw, T dt, int batch) {
     constexpr int NX = P::NX, NU = P::NU, PW = 64 / A;
     static_assert(64 % A == 0 && PW * NX <= 64, "a wavefront holds whole problems; one fetch per lane for the state");
     const int lane = threadIdx.x, grp = lane / A, a_idx = lane - grp * A, pb0 = blockIdx.x * PW, N = dm.N;
@@ -548,7 +559,19 @@ template <typename P, int INTEG, typename T, int A>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? PDDP_FPCF_WAVES : 1))) void k_fp_cf(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int batch) {
     __shared__ FpCfStage<P, T, A> stage[2];
     __shared__ T goal_s[64 / A][P::NX];
-    fp_cf_body<P, INTEG, T, A, 1>(stage, goal_s, b, dm, cw, dt, batch);
+    if constexpr (IsDiagTab<P>::value) {
+        // the records of the wavefront's 64 / A problems are staged in LDS once (next to their goals) and every step's cost reads its lane's problem's copy there:
+        // no weight is held in a register across the step loop
+        constexpr int PW = 64 / A, REC = P::REC;
+        __shared__ T rec_s[PW][REC];
+        const int lane = threadIdx.x, pb0 = blockIdx.x * PW;
+        for (int e = lane; e < PW * REC; e += 64) { const int p = e / REC, q = (pb0 + p < batch) ? pb0 + p : batch - 1; (&rec_s[0][0])[e] = b.cwt[(size_t)q * REC + (e - p * REC)]; }
+        wsync();
+        const DiagCostWeights<T> own = diag_cost_weights(cw, &rec_s[lane / A][0]);
+        fp_cf_body<P, INTEG, T, A, 1>(stage, goal_s, b, dm, own, dt, batch);
+    } else {
+        fp_cf_body<P, INTEG, T, A, 1>(stage, goal_s, b, dm, cw, dt, batch);
+    }
 }
 template <typename P, int INTEG, typename T, int A>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? PDDP_SWEEPCF_WAVES : 1))) void k_sweep_cf(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int batch) {
@@ -561,7 +584,12 @@ __global__ __launch_bounds__(64) void k_nis_ts(Buffers<T> b, Dims dm, CostWeight
     const int inst = blockIdx.x * 64 + threadIdx.x;
     if (inst >= batch * dm.N) return;
     NisScratch<P, INTEG, T> s;
-    nis_body<P, INTEG, T>(serial_wave(), s, b, dm, cw, dt, mode, inst % dm.N, inst / dm.N);
+    if constexpr (IsDiagTab<P>::value) {
+        const DiagCostWeights<T> own = diag_cost_weights(cw, b.cwt + (size_t)(inst / dm.N) * P::REC);
+        nis_body<P, INTEG, T>(serial_wave(), s, b, dm, own, dt, mode, inst % dm.N, inst / dm.N);
+    } else {
+        nis_body<P, INTEG, T>(serial_wave(), s, b, dm, cw, dt, mode, inst % dm.N, inst / dm.N);
+    }
 }
 
 // In between for the larger closed-form plants (quadrotor: 12 states, 16 columns of [A B]): G lanes per unit, 64 / G units per wavefront, the SAME bodies with a
@@ -576,7 +604,12 @@ __global__ __launch_bounds__(64) void k_nis_gl(Buffers<T> b, Dims dm, CostWeight
     __shared__ NisScratch<P, INTEG, T> s[U];
     const int grp = threadIdx.x / G, inst = blockIdx.x * U + grp;
     if (inst >= batch * dm.N) return;
-    nis_body<P, INTEG, T>(Wave{(int)threadIdx.x & (G - 1), G, 0}, s[grp], b, dm, cw, dt, mode, inst % dm.N, inst / dm.N);
+    if constexpr (IsDiagTab<P>::value) {                               // a lane reads the one weight of its entry of g_k / H_k from its unit's problem's row
+        const DiagCostWeights<T> own = diag_cost_weights(cw, b.cwt + (size_t)(inst / dm.N) * P::REC);
+        nis_body<P, INTEG, T>(Wave{(int)threadIdx.x & (G - 1), G, 0}, s[grp], b, dm, own, dt, mode, inst % dm.N, inst / dm.N);
+    } else {
+        nis_body<P, INTEG, T>(Wave{(int)threadIdx.x & (G - 1), G, 0}, s[grp], b, dm, cw, dt, mode, inst % dm.N, inst / dm.N);
+    }
 }
 template <typename P, typename T, int G>
 __global__ __launch_bounds__(64) void k_bp_gl(Buffers<T> b, Dims dm, int batch) {
@@ -605,6 +638,7 @@ __global__ __launch_bounds__(64) void k_bp_gl(Buffers<T> b, Dims dm, int batch) 
 // No barrier inside a phase; one between them (a one-wave block).
 template <typename P> struct GradZeroCols { static constexpr unsigned value = 0u; };                                    // bit c: column c of dynamicsGradient's dqdd is identically zero
 template <typename T> struct GradZeroCols<QuadPlant<T>> { static constexpr unsigned value = 0x1C7u; };                  // x y z and their rates (plants/dynamics_quad.cuh:75-169 never writes them; tests/test_closed_form_pins.py)
+template <typename B, typename T> struct GradZeroCols<DiagTab<B, T>> : GradZeroCols<B> {};                               // (the same dynamics)
 template <typename P> struct GradCols {
     static constexpr int NM = P::NX + P::NU;
     static constexpr unsigned zero = GradZeroCols<P>::value;
@@ -661,7 +695,7 @@ __global__ __launch_bounds__(64) void k_nis_kb(Buffers<T> b, Dims dm, CostWeight
                         else {
                             T gv[NM], xgv[NX];
                             cf_load_vec<T, NX>(xgv, xg);
-                            PDDP_UNROLL for (int i = 0; i < NM; i++) gv[i] = P::weight(cw, i, k, N) * (i < NX ? (x[i] - xgv[i]) : u[i - NX]);
+                            PDDP_UNROLL for (int i = 0; i < NM; i++) gv[i] = knot_weight<P, T>(b, cw, pb, i, k, N) * (i < NX ? (x[i] - xgv[i]) : u[i - NX]);
                             cf_store_vec<T, NM>(gk, gv);
                         }
                     }
@@ -731,7 +765,7 @@ __global__ __launch_bounds__(64) void k_nis_kb(Buffers<T> b, Dims dm, CostWeight
             if (mode == 1) {                                                            // the constant Hessian: written when the problem is loaded (nis_knot, nis.hpp)
                 T* Hk = b.H + ((size_t)pb * N + k) * NM * NM + (size_t)ky * NM;
                 T hv[NM];
-                PDDP_UNROLL for (int i = 0; i < NM; i++) hv[i] = (i == ky) ? P::weight(cw, i, k, N) : T(0);
+                PDDP_UNROLL for (int i = 0; i < NM; i++) hv[i] = (i == ky) ? knot_weight<P, T>(b, cw, pb, i, k, N) : T(0);
                 cf_store_vec<T, NM>(Hk, hv);
             }
         }
@@ -827,7 +861,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) ==
     a.dJexp = b.dJexp + (size_t)pb * 2 * dm.M;
     a.err = b.err + (size_t)pb * dm.M;
     a.rho = st.rho;
-    if (bp_cl_block<P, T>(s[grp], c, dm, blk, a, diag_h != 0, P::weight(cw, c, 0, N))) { if (c == 0) a.err[blk] = 1; }
+    if (bp_cl_block<P, T>(s[grp], c, dm, blk, a, diag_h != 0, knot_weight<P, T>(b, cw, pb, c, 0, N))) { if (c == 0) a.err[blk] = 1; }
 }
 
 // k_bp_mq: one wavefront = (problem, block of knots) of a 12-state / 4-control plant on the matrix cores (bp_mq.hpp); grid B M, block 64.  Replaces backPassKern<<<M, ...>>>
@@ -1014,7 +1048,12 @@ __global__ __launch_bounds__(64) void k_init_cost(Buffers<T> b, Dims dm, CostWei
                                                   int stage, int keep_alpha) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     if constexpr (P::PLANT == 4) cw = cost_weights_at(b, cw, (int)blockIdx.x);      // the problem's own weights (uniform: scalar loads)
-    init_cost_body<P, T>(this_wave(), reinterpret_cast<T*>(lds_raw), b, dm, cw, sp, ignore_first_defect, rollout, blockIdx.x, stage, keep_alpha);
+    if constexpr (IsDiagTab<P>::value) {
+        const DiagCostWeights<T> own = diag_cost_weights(cw, b.cwt + (size_t)blockIdx.x * P::REC);      // (uniform row: scalar loads)
+        init_cost_body<P, T>(this_wave(), reinterpret_cast<T*>(lds_raw), b, dm, own, sp, ignore_first_defect, rollout, blockIdx.x, stage, keep_alpha);
+    } else {
+        init_cost_body<P, T>(this_wave(), reinterpret_cast<T*>(lds_raw), b, dm, cw, sp, ignore_first_defect, rollout, blockIdx.x, stage, keep_alpha);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------- plant evaluation (tests / tools)

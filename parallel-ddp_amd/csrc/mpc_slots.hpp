@@ -30,7 +30,7 @@ struct MpcSlotSide {                 // one side (handle or intake area) of the 
 
 template <int NX, int NU, typename T>
 bool mpc_slot_tables(std::vector<SlotTable>& in_t, std::vector<SlotTable>& out_t, const Buffers<T>& ib, const MpcBuffers<T>& imb, const MpcSlotSide<T>& is,
-                     const Buffers<T>& b, const MpcBuffers<T>& mb, const MpcSlotSide<T>& hs, int Nk, int Mk, int Ak, int max_iter, int ee_cost) {
+                     const Buffers<T>& b, const MpcBuffers<T>& mb, const MpcSlotSide<T>& hs, int Nk, int Mk, int Ak, int max_iter, int ee_cost, int cwt_rec = 0) {      // cwt_rec: numbers per row of the cost table; 0: the arm's record of its cost family
     constexpr size_t NM = NX + NU;
     const size_t N = Nk, M = Mk, A = Ak, out = (size_t)max_iter + 2, e = sizeof(T);
     bool ok = true;
@@ -61,7 +61,7 @@ bool mpc_slot_tables(std::vector<SlotTable>& in_t, std::vector<SlotTable>& out_t
     add(2, ib.xGoal, b.xGoal, NX * e); add(2, ib.tshift, b.tshift, sizeof(int)); add(3, ib.costk, b.costk, N * e);
     add(3, ib.Jout, b.Jout, out * e); add(3, ib.alphaOut, b.alphaOut, out * sizeof(int));
     add(1, ib.xTarget, b.xTarget, NX * e);
-    if (hs.cwt_rows) add(1, is.cwt_rows, hs.cwt_rows, cost_record_len(ee_cost) * e);
+    if (hs.cwt_rows) add(1, is.cwt_rows, hs.cwt_rows, (cwt_rec ? cwt_rec : cost_record_len(ee_cost)) * e);
     add(2, is.xActual, hs.xActual, NX * e); add(2, is.goal_in, hs.goal_in, NX * e); add(2, is.shift, hs.shift, sizeof(int));
     return ok;
 }

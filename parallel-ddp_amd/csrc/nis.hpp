@@ -23,9 +23,9 @@ struct NisScratch {
 };
 
 // xk/uk: the knot's state and control (global).  Writes ABk (k < N-1), Hk, gk (global).
-template <typename P, int INTEG, typename T>
+template <typename P, int INTEG, typename T, typename CW = CostWeights<T>>      // CW: the record as the plant's cost routines take it (plants.hpp DiagCostWeights for a DiagTab plant)
 PDDP_HD void nis_knot(const Wave& w, NisScratch<P, INTEG, T>& s, const Dims& dm, int k, const T* xk, const T* uk, const T* xg,
-                      const CostWeights<T>& cw, T dt, T* ABk, T* Hk, T* gk, const T* xt = nullptr, int tshift = 0, T* cost_out = nullptr, bool write_const_H = true) {
+                      const CW& cw, T dt, T* ABk, T* Hk, T* gk, const T* xt = nullptr, int tshift = 0, T* cost_out = nullptr, bool write_const_H = true) {
     constexpr int NX = P::NX, NU = P::NU, NM = NX + NU;
     PDDP_FOR(i, NX) s.x[i] = xk[i];
     PDDP_FOR(i, NU) s.u[i] = uk[i];

@@ -122,6 +122,15 @@ extern "C" int pddp_get_cost_problems(pddp_handle h, int count, const int* idx, 
     if (int rc = cost_problems_check(s, "pddp_get_cost_problems", count, idx, w, false)) return rc;
     return s->get_cost_problems(count, idx, w);
 }
+// run-time diagonal cost weights of the pendulum, cart-pole and quadrotor (diag_cost_table.hpp): the handle checks every argument in its element type before it is touched
+extern "C" int pddp_diag_cost_size(pddp_handle h) {
+    IMPL(h);
+    const int rec = s->diag_cost_size();
+    return rec ? rec : fail(PDDP_EINVAL, "pddp_diag_cost_size: diagonal cost records belong to the pendulum, cart-pole and quadrotor (plants 1-3)");
+}
+extern "C" int pddp_set_diag_cost(pddp_handle h, const double* w) { IMPL(h); return s->set_diag_cost(w); }
+extern "C" int pddp_set_diag_cost_problems(pddp_handle h, int count, const int* idx, const double* w) { IMPL(h); return s->set_diag_cost_problems(count, idx, w); }
+extern "C" int pddp_get_diag_cost_problems(pddp_handle h, int count, const int* idx, double* w) { IMPL(h); return s->get_diag_cost_problems(count, idx, w); }
 extern "C" int pddp_simulate(pddp_handle h, const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps, const void* goal_xyz,
                              void* xActual_inout, double* avg_err, int* failed) {
     IMPL(h); if (!x || !u || !KT || !xActual_inout) return fail(PDDP_EINVAL, "null argument");

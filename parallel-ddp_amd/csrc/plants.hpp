@@ -14,7 +14,7 @@
 namespace pddp {
 
 template <typename T>
-struct CostWeights {   // arm joint-space weights (plants/cost_arm.cuh:97-103); other plants use fixed macros
+struct CostWeights {   // arm joint-space weights (plants/cost_arm.cuh:97-103); the other plants' diagonal weights are literals or a row of Buffers::cwt (DiagTab below)
     T Q1, Q2, R, QF1, QF2;
     // end-effector cost family (EE_COST 1, plants/cost_arm.cuh:206-389; ee_cost.hpp): xyz / rpy running and final weights, control weight,
     // nominal-state weights on q and qd, and the tool point's offset along the last link's z axis (EE_ON_LINK_Z, dynamics_arm.cuh:53-65)
@@ -224,6 +224,53 @@ template <typename T> PDDP_HD double CartPlant<T>::QF(int N) { return N == 512 ?
 template <typename T> PDDP_HD double QuadPlant<T>::QR(int i, int) { return i < 3 ? 0.01 : (i < 6 ? 0.001 : (i < 9 ? 2.0 : (i < 12 ? 2.0 : 5.0))); }
 template <typename T> PDDP_HD double QuadPlant<T>::Rw(int) { return 5.0; }
 template <typename T> PDDP_HD double QuadPlant<T>::QF(int) { return 1000.0; }
+
+// ---- run-time diagonal cost weights of the pendulum, cart-pole and quadrotor (pddp_set_diag_cost / pddp_set_diag_cost_problems) ----
+// The record of a problem is the diagonal of its cost, [ q_0..q_{NX-1} | r_0..r_{NU-1} | qf_0..qf_{NX-1} ] in the handle's element type; Buffers::cwt is null (the
+// weights are the literals above) or a table [batch][2 NX + NU] (diag_cost_table.hpp).  DiagTab<B, T> is plant B with cost(), cost_grad() and weight() reading such a
+// record instead of QR / Rw / QF: the SAME source expressions with the run-time T in place of (T)literal.  It is a plant policy of its own, so every kernel that serves
+// a handle with a table is an instantiation of its own and the instantiations on B are the ones they always were.
+// The policy's cost routines take a DiagCostWeights -- the handle's record + the row's address (global memory, or the copy a kernel staged in LDS) -- and nothing
+// else: a kernel of a DiagTab plant builds one and hands it to its bodies, which pass the record on in the type they were given (their CW parameter).  The plain
+// CostWeights kernel argument does not convert to it, so a call that would have no row does not compile; lanes that look a weight up themselves use knot_weight.
+template <typename T>
+struct DiagCostWeights : CostWeights<T> { const T* row; };
+template <typename T>
+PDDP_HD DiagCostWeights<T> diag_cost_weights(const CostWeights<T>& cw, const T* row) {
+    DiagCostWeights<T> o{};
+    o.fd_eps = cw.fd_eps;            // (the only field a closed-form plant's kernels read)
+    o.row = row;
+    return o;
+}
+template <typename B, typename T>
+struct DiagTab : B {
+    static constexpr int NX = B::NX, NU = B::NU, REC = 2 * B::NX + B::NU;
+    template <typename U> using Rebind = DiagTab<typename B::template Rebind<U>, U>;
+    static PDDP_HD T weight_row(const T* r, int i, int k, int N) { return k == N - 1 ? (i < NX ? r[NX + NU + i] : T(0)) : r[i]; }
+    static PDDP_HD T weight(const DiagCostWeights<T>& cw, int i, int k, int N) { return weight_row(cw.row, i, k, N); }
+    static PDDP_HD T cost(const DiagCostWeights<T>& cw, const T* xk, const T* uk, const T* xg, int k, int N) {      // diag_cost
+        const T* r = cw.row;
+        T cost = 0.0;
+        for (int i = 0; i < NX; i++) { const double dl = xk[i] - xg[i]; cost += (k == N - 1 ? r[NX + NU + i] : r[i]) * (dl * dl); }
+        if (k != N - 1) for (int i = 0; i < NU; i++) { const double uu = uk[i]; cost += r[NX + i] * (uu * uu); }
+        return 0.5 * cost;
+    }
+    static PDDP_HD void cost_grad(const DiagCostWeights<T>& cw, T* Hk, T* gk, const T* xk, const T* uk, const T* xg, int k, int N) {      // diag_cost_grad
+        constexpr int NM = NX + NU;
+        const T* r = cw.row;
+        for (int i = 0; i < NM; i++) for (int j = 0; j < NM; j++) Hk[i * NM + j] = i != j ? T(0) : weight_row(r, i, k, N);
+        for (int i = 0; i < NX; i++) gk[i] = (k == N - 1 ? r[NX + NU + i] : r[i]) * (xk[i] - xg[i]);
+        for (int i = 0; i < NU; i++) gk[i + NX] = (k == N - 1 ? T(0) : r[NX + i]) * uk[i];
+    }
+};
+template <typename P> struct IsDiagTab { static constexpr bool value = false; };
+template <typename B, typename T> struct IsDiagTab<DiagTab<B, T>> { static constexpr bool value = true; };
+// weight(i, k) of problem pb for the kernels whose lanes look the weight up themselves (k_nis_kb, k_bp_cl, k_bp_mq): the policy's literal, or the entry of the table's row
+template <typename P, typename T>
+PDDP_HD T knot_weight(const Buffers<T>& b, const CostWeights<T>& cw, int pb, int i, int k, int N) {
+    if constexpr (IsDiagTab<P>::value) return P::weight_row(b.cwt + (size_t)pb * P::REC, i, k, N);
+    else return P::weight(cw, i, k, N);
+}
 
 // A scalar plug-in's gradient routine also returns qdd; the kernel families build the midpoint / RK3 stage states from that qdd (serial paths) or from the dynamics routine's
 // (the staged three-lane path of integrators.hpp), so the two have to be the SAME numbers -- the reference's plug-ins call dynamics() inside dynamicsGradient.  Checked on the

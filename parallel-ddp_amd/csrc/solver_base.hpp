@@ -60,6 +60,11 @@ struct SolverBase {
     virtual int cost_record_size() const = 0;      // 5 (joint-space cost) or 9 (end-effector cost); 0: the handle's plant has no weights to set
     virtual int set_cost_problems(int count, const int* idx, const double* w) = 0;
     virtual int get_cost_problems(int count, const int* idx, double* w) = 0;
+    // run-time diagonal cost weights of the pendulum, cart-pole and quadrotor (diag_cost_table.hpp); these check their own arguments (the checks depend on the element type)
+    virtual int diag_cost_size() const = 0;        // 2 NX + NU; 0: the handle's plant has no diagonal record (plants 4 and 5)
+    virtual int set_diag_cost(const double* w) = 0;
+    virtual int set_diag_cost_problems(int count, const int* idx, const double* w) = 0;
+    virtual int get_diag_cost_problems(int count, const int* idx, double* w) = 0;
     virtual int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
                           int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) = 0;
     virtual int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) = 0;   // mpc_solve's load stage alone (teacher-forcing hook)

@@ -6,6 +6,7 @@
 #include "handle_setup.hpp"
 #include "slots.hpp"
 #include "cost_table.hpp"
+#include "diag_cost_table.hpp"
 #include "mpc_slots.hpp"
 #include "tl_launch.hpp"
 #include "mx_launch.hpp"
@@ -346,7 +347,7 @@ struct Solver : SolverBase {
         const int ee = cfg.ee_cost ? 1 : 0;                          // end-effector cost: the initial cost comes out of the setup kernel (stage 2)
         HIPCHK(hipMemsetAsync(b.tshift, 0, B * sizeof(int), stream));
         if (rollout) {                                               // forwardRolloutFlag (:642-648)
-            hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), stream, b, dm, cw, sp, ignore_first_defect, 1, ee, 0);   // state.cur = 0
+            launch_init_cost(stream, ignore_first_defect, 1, ee, 0);   // state.cur = 0
             launch_fp(stream, 1);
             hipLaunchKernelGGL((k_adopt_slot0<P, T>), dim3(N, B), dim3(64), 0, stream, b, dm);
         }
@@ -356,12 +357,17 @@ struct Solver : SolverBase {
     }
     // what starts a solve from the loaded trajectory: initial cost, setup kernel in init mode and, for the end-effector cost, the cost's second pass (its initial cost comes
     // out of the setup kernel).  keep_alpha: the MPC call keeps alphaIndex (runiLQR_MPC_GPU does not reset it)
+    void launch_init_cost(hipStream_t s, int ignore_first_defect, int rollout, int stage, int keep_alpha) {
+        with_cost_plant([&](auto pl) {
+            using Q = decltype(pl);
+            hipLaunchKernelGGL((k_init_cost<Q, T>), dim3(cfg.batch), dim3(64), (size_t)cfg.N * sizeof(T), s, b, dm, cw, sp, ignore_first_defect, rollout, stage, keep_alpha);
+        });
+    }
     void launch_init_cost_and_setup(hipStream_t s, int ignore_first_defect, int rollout, int keep_alpha) {
-        const unsigned B = cfg.batch; const size_t N = cfg.N;
         const int ee = cfg.ee_cost ? 1 : 0;
-        hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), s, b, dm, cw, sp, ignore_first_defect, rollout, ee, keep_alpha);
+        launch_init_cost(s, ignore_first_defect, rollout, ee, keep_alpha);
         launch_nis(s, 1);
-        if (ee) hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), N * sizeof(T), s, b, dm, cw, sp, ignore_first_defect, rollout, 2, keep_alpha);
+        if (ee) launch_init_cost(s, ignore_first_defect, rollout, 2, keep_alpha);
     }
     // forward pass: the arm runs on lane groups (fp_lg.hpp), the closed-form plants on the wave-cooperative kernel
     // part: -1 everything; 0 only the linear sweep kernel (when the path has a separate one); 1 only the rollout kernel (per-kernel timing; kernels that sweep
@@ -386,22 +392,22 @@ struct Solver : SolverBase {
                 if constexpr (P::kScalarPlugin && (64 / 16) * P::NX <= 64) {
                     if (records && cfg.A == 16) {
                         if (part != 1 && cfg.M > 1) { if (!launch_sweep_maps_cf(s)) hipLaunchKernelGGL((k_sweep_cf<P, INTEG, T, 16>), dim3((B + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, (int)B); }
-                        if (part != 0) hipLaunchKernelGGL((k_fp_cf<P, INTEG, T, 16>), dim3((B + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, (int)B);
+                        if (part != 0) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, 16>), dim3((B + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, (int)B); });
                         return;
                     }
                 }
                 if constexpr (P::kScalarPlugin && (64 / 8) * P::NX <= 64) {
                     if (records && cfg.A == 8) {
                         if (part != 1 && cfg.M > 1) { if (!launch_sweep_maps_cf(s)) hipLaunchKernelGGL((k_sweep_cf<P, INTEG, T, 8>), dim3((B + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, (int)B); }
-                        if (part != 0) hipLaunchKernelGGL((k_fp_cf<P, INTEG, T, 8>), dim3((B + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, (int)B);
+                        if (part != 0) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, 8>), dim3((B + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, (int)B); });
                         return;
                     }
                 }
                 if (part == 0) return;                                  // (the paths below sweep inside their rollout kernel)
-                if (!serial && cf_fp && !init_rollout) { hipLaunchKernelGGL((k_fp_ts<P, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, part == 2 ? 1 : 0); serial = true; }
+                if (!serial && cf_fp && !init_rollout) { with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, part == 2 ? 1 : 0); }); serial = true; }
             }
             if (part == 0) return;
-            if (!serial) hipLaunchKernelGGL((k_fp<P, INTEG, T>), dim3(init_rollout ? 1 : cfg.A, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, init_rollout ? 1 : (part == 2 ? 2 : 0));
+            if (!serial) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(init_rollout ? 1 : cfg.A, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, init_rollout ? 1 : (part == 2 ? 2 : 0)); });
             if constexpr (P::PLANT != 4) { if (b.xw && !records_ran && !init_rollout) hipLaunchKernelGGL((k_cand_to_xw<P, T>), dim3((unsigned)(((size_t)B * cfg.N * cfg.A + 255) / 256)), dim3(256), 0, s, b, dm, (int)B); }
             return;
         }
@@ -469,20 +475,23 @@ struct Solver : SolverBase {
             }
         }
         if (part == 0) return;
-        if constexpr (P::PLANT != 4) { if (cf_nis) { hipLaunchKernelGGL((k_nis_ts<P, INTEG, T>), dim3((B * cfg.N + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); return; } }
+        if constexpr (P::PLANT != 4) { if (cf_nis) { with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis_ts<Q, INTEG, T>), dim3((B * cfg.N + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); }); return; } }
         if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16 && INTEG == 3 && P::kScalarPlugin) {
             if (gl_nis && kb_nis) {
                 const int units = (int)(B * cfg.N);
-                if (kb_nis == 16) hipLaunchKernelGGL((k_nis_kb<P, T, 16>), dim3((units + 15) / 16), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
-                else if (kb_nis == 20) hipLaunchKernelGGL((k_nis_kb<P, T, 20>), dim3((units + 19) / 20), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
-                else if (kb_nis == 64 && sizeof(T) == 4) hipLaunchKernelGGL((k_nis_kb<P, T, sizeof(T) == 4 ? 64 : 16>), dim3((units + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
-                else hipLaunchKernelGGL((k_nis_kb<P, T, 32>), dim3((units + 31) / 32), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                with_cost_plant([&](auto pl) {
+                    using Q = decltype(pl);
+                    if (kb_nis == 16) hipLaunchKernelGGL((k_nis_kb<Q, T, 16>), dim3((units + 15) / 16), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                    else if (kb_nis == 20) hipLaunchKernelGGL((k_nis_kb<Q, T, 20>), dim3((units + 19) / 20), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                    else if (kb_nis == 64 && sizeof(T) == 4) hipLaunchKernelGGL((k_nis_kb<Q, T, sizeof(T) == 4 ? 64 : 16>), dim3((units + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                    else hipLaunchKernelGGL((k_nis_kb<Q, T, 32>), dim3((units + 31) / 32), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                });
                 return;
             }
         }
-        if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) { if (gl_nis) { if (gl_nis8) hipLaunchKernelGGL((k_nis_gl<P, INTEG, T, 8>), dim3((B * cfg.N + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); else hipLaunchKernelGGL((k_nis_gl<P, INTEG, T, 16>), dim3((B * cfg.N + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); return; } }
+        if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) { if (gl_nis) { with_cost_plant([&](auto pl) { using Q = decltype(pl); if (gl_nis8) hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 8>), dim3((B * cfg.N + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); else hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 16>), dim3((B * cfg.N + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); }); return; } }
         if constexpr (P::PLANT == 4) { if (b.cwt) { hipLaunchKernelGGL((k_nis<P, INTEG, T, true>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); return; } }
-        hipLaunchKernelGGL((k_nis<P, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode);
+        with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis<Q, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); });
     }
     void launch_sweep(hipStream_t s, int only = -1, int store_candidates = 0, int part = -1) {
         const unsigned B = cfg.batch;
@@ -507,15 +516,16 @@ struct Solver : SolverBase {
                     if (!serial && gl_bp && cl_bp && mq_bp) {
                         const bool fu = mq_fused && (!store_candidates || phase_fused_sweep);      // (the phase hook's backward pass writes A - B K / B du: its sweep is teacher-forced from them)
                         const bool dh = !P::kPluginCost && !h_overridden;   // the plant's own diagonal cost Hessian: not read
-                        if (dh && fu) hipLaunchKernelGGL((k_bp_mq<P, T, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
-                        else if (dh) hipLaunchKernelGGL((k_bp_mq<P, T, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
+                        // (only the instantiations that take the running knots' Hessian from the weights differ with a table of diagonal records: the others read H)
+                        if (dh && fu) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
+                        else if (dh) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
                         else if (fu) hipLaunchKernelGGL((k_bp_mq<P, T, false, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
                         else hipLaunchKernelGGL((k_bp_mq<P, T, false>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
                         serial = true;
                     }
                 }
                 if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4) {
-                    if (!serial && gl_bp && cl_bp) { hipLaunchKernelGGL((k_bp_cl<P, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, cw, (int)B, (!P::kPluginCost && !h_overridden) ? 1 : 0); serial = true; }
+                    if (!serial && gl_bp && cl_bp) { with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_cl<Q, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, cw, (int)B, (!P::kPluginCost && !h_overridden) ? 1 : 0); }); serial = true; }
                 }
                 if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) { if (!serial && gl_bp) { if (gl_bp32) hipLaunchKernelGGL((k_bp_gl<P, T, 32>), dim3((B * cfg.M + 1) / 2), dim3(64), 0, s, b, dm, (int)B); else hipLaunchKernelGGL((k_bp_gl<P, T, 16>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, (int)B); serial = true; } }
                 if (serial) {}
@@ -657,7 +667,7 @@ struct Solver : SolverBase {
     int cost_record_size() const override { return P::PLANT == 4 && !P::kPluginCost ? cost_record_len(cfg.ee_cost) : 0; }
     // every row <- the handle-wide record (a table that exists: pddp_set_cost / pddp_set_cost_ee after per-problem weights; the last call wins)
     int fill_cost_table() {
-        if (!d_cwt) return 0;
+        if (!d_cwt || kDiagCost) return 0;                          // (plants 1-3: the table holds diagonal records, which pddp_set_cost has no part in -- the call is as inert there as it always was)
         const int rec = cost_record_len(cfg.ee_cost);
         cwt_stage.resize((size_t)cfg.batch * rec);
         for (int i = 0; i < cfg.batch; i++) cost_record_of<T>(cw, cwt_stage.data() + (size_t)i * rec);
@@ -665,10 +675,12 @@ struct Solver : SolverBase {
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
+    // numbers per row of the table: the arm's record of its cost family, or the diagonal record of the pendulum, cart-pole and quadrotor
+    int table_record_len() const { return kDiagCost ? kDiagRec : cost_record_len(cfg.ee_cost); }
     int ensure_cost_table(int rows) {
         if (d_cwt) return 0;
         void* p = nullptr;
-        if (hipMalloc(&p, (size_t)rows * cost_record_len(cfg.ee_cost) * sizeof(T)) != hipSuccess) return fail(PDDP_ENOMEM, "hipMalloc failed for the per-problem cost weights");
+        if (hipMalloc(&p, (size_t)rows * table_record_len() * sizeof(T)) != hipSuccess) return fail(PDDP_ENOMEM, "hipMalloc failed for the per-problem cost weights");
         allocs.push_back(p); d_cwt = (T*)p;
         return 0;
     }
@@ -705,6 +717,83 @@ struct Solver : SolverBase {
             HIPCHK(hipStreamSynchronize(stream));
         } else for (int i = 0; i < count; i++) cost_record_of<T>(cw, cwt_stage.data() + (size_t)i * rec);
         for (size_t e = 0; e < (size_t)count * rec; e++) w[e] = (double)cwt_stage[e];
+        return 0;
+    }
+    // ---- run-time diagonal cost weights of the pendulum, cart-pole and quadrotor (diag_cost_table.hpp, plants.hpp DiagTab): pddp_set_diag_cost* / pddp_get_diag_cost_problems
+    // The same table machinery (d_cwt, b.cwt, the intake fetch) with rows of 2 NX + NU numbers.  Without a table every launch below is the one it always was; with one,
+    // every kernel that reads a weight runs in its DiagTab instantiation (with_cost_plant), which takes problem pb's weights from row pb.
+    static constexpr bool kDiagCost = P::PLANT >= 1 && P::PLANT <= 3;
+    static constexpr int kDiagRec = 2 * NX + NU;
+    int diag_cost_size() const override { return kDiagCost ? kDiagRec : 0; }
+    // f(plant policy): DiagTab<P, T> for a handle with a table of diagonal records, P otherwise (the arm's per-problem weights are a run-time branch inside its kernels)
+    template <typename F> void with_cost_plant(F&& f) {
+        if constexpr (kDiagCost) { if (b.cwt) { f(DiagTab<P, T>{}); return; } }
+        f(P{});
+    }
+    int diag_refuse(const char* who) { return fail(PDDP_EINVAL, std::string(who) + ": diagonal cost records belong to the pendulum, cart-pole and quadrotor (plants 1-3); the arm has pddp_set_cost_problems, a plug-in plant its own cost file"); }
+    // first setter call: the table, every row the built-in record; b.cwt; the captured graph goes once (other kernels, another argument)
+    int ensure_diag_table() {
+        if (b.cwt) return 0;                                        // (keyed on what the kernels see: a first call that failed half way is done again in full)
+        if constexpr (kDiagCost) {
+            T row[kDiagRec];
+            if (!diag_record_builtin<P, T>(cfg.N, row)) return fail(PDDP_EINVAL, "diagonal cost records: the plant's QR(NX + j, N) differs from its Rw(N), so its control weight is not one number");
+            if (int rc = ensure_cost_table(cfg.batch)) return rc;
+            cwt_stage.resize((size_t)cfg.batch * kDiagRec);
+            for (int i = 0; i < cfg.batch; i++) std::memcpy(cwt_stage.data() + (size_t)i * kDiagRec, row, sizeof(row));
+            HIPCHK(hipMemcpyAsync(d_cwt, cwt_stage.data(), cwt_stage.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipStreamSynchronize(stream));                   // (nothing in flight reads the old argument set)
+            if (fp_lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fp<DiagTab<P, T>, INTEG, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp_lds));
+            b.cwt = d_cwt;
+            drop_graph();
+        }
+        return 0;
+    }
+    int set_diag_cost_problems(int count, const int* idx, const double* w) override {
+        if (!kDiagCost) return diag_refuse("pddp_set_diag_cost_problems");
+        const std::string complaint = diag_records_complaint<T>(count, idx, w, cfg.batch, NX, NU);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_diag_cost_problems: " + complaint);
+        if (int rc = ensure_diag_table()) return rc;
+        cwt_stage.resize((size_t)count * kDiagRec);
+        cost_records_pack<T>(count, kDiagRec, w, cwt_stage.data());
+        for (int i = 0; i < count;) {                               // contiguous runs of slots go up in one transfer each; rows that are not named keep their values
+            int j = i + 1;
+            while (j < count && idx[j] == idx[j - 1] + 1) j++;
+            HIPCHK(hipMemcpyAsync(d_cwt + (size_t)idx[i] * kDiagRec, cwt_stage.data() + (size_t)i * kDiagRec, (size_t)(j - i) * kDiagRec * sizeof(T), hipMemcpyHostToDevice, stream));
+            i = j;
+        }
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int set_diag_cost(const double* w) override {
+        if (!kDiagCost) return diag_refuse("pddp_set_diag_cost");
+        const int zero = 0;
+        const std::string complaint = diag_records_complaint<T>(1, &zero, w, cfg.batch, NX, NU);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_diag_cost: " + complaint);
+        if (int rc = ensure_diag_table()) return rc;
+        cwt_stage.resize((size_t)cfg.batch * kDiagRec);
+        cost_records_pack<T>(1, kDiagRec, w, cwt_stage.data());
+        for (int i = 1; i < cfg.batch; i++) std::memcpy(cwt_stage.data() + (size_t)i * kDiagRec, cwt_stage.data(), kDiagRec * sizeof(T));
+        HIPCHK(hipMemcpyAsync(d_cwt, cwt_stage.data(), cwt_stage.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int get_diag_cost_problems(int count, const int* idx, double* w) override {
+        if (!kDiagCost) return diag_refuse("pddp_get_diag_cost_problems");
+        const std::string complaint = diag_records_complaint<T>(count, idx, w, cfg.batch, NX, NU, false);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_get_diag_cost_problems: " + complaint);
+        cwt_stage.resize((size_t)count * kDiagRec);
+        if (d_cwt) {
+            for (int i = 0; i < count;) {
+                int j = i + 1;
+                while (j < count && idx[j] == idx[j - 1] + 1) j++;
+                HIPCHK(hipMemcpyAsync(cwt_stage.data() + (size_t)i * kDiagRec, d_cwt + (size_t)idx[i] * kDiagRec, (size_t)(j - i) * kDiagRec * sizeof(T), hipMemcpyDeviceToHost, stream));
+                i = j;
+            }
+            HIPCHK(hipStreamSynchronize(stream));
+        } else if constexpr (kDiagCost) {
+            for (int i = 0; i < count; i++) diag_record_builtin<P, T>(cfg.N, cwt_stage.data() + (size_t)i * kDiagRec);
+        }
+        for (size_t e = 0; e < (size_t)count * kDiagRec; e++) w[e] = (double)cwt_stage[e];
         return 0;
     }
     // The load stage of a control cycle, enqueued: argument checks, pinned staging, the single input transfer and the k_mpc_load launch.  pddp_mpc_solve goes on
@@ -963,7 +1052,7 @@ struct Solver : SolverBase {
         fetch.n = 0; fetch.N = cfg.N; fetch.state = nullptr; fetch.state_stride = fetch.off_cur = fetch.off_alpha = 0;
         if (cfg.ee_cost) slot_add(fetch, in.b.xTarget, b.xTarget, NX * sizeof(T), NX * sizeof(T), NX * sizeof(T), kSlotCopy);      // the slots' own nominal-state targets: read by the setup kernel, not part of a load
         if (b.cwt) {                                                 // ... and their own cost weights: rows idx[c0 .. c0 + n) of the handle's table -> rows 0 .. n of the intake's
-            const size_t rb = cost_record_len(cfg.ee_cost) * sizeof(T);
+            const size_t rb = table_record_len() * sizeof(T);
             if (!slot_add(fetch, in.d_cwt, d_cwt, rb, rb, rb, kSlotCopy)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
         }
         const size_t N = cfg.N;
@@ -1031,7 +1120,7 @@ struct Solver : SolverBase {
     bool cycle_tables(std::vector<SlotTable>& in_t, std::vector<SlotTable>& out_t) {
         const Solver& in = *intake;
         const MpcSlotSide<T> is{b.cwt ? in.d_cwt : nullptr, in.d_xActual, in.d_goal_in, in.d_shift}, hs{b.cwt ? d_cwt : nullptr, d_xActual, d_goal_in, d_shift};
-        return mpc_slot_tables<NX, NU, T>(in_t, out_t, in.b, in.mb, is, b, mb, hs, cfg.N, cfg.M, cfg.A, cfg.max_iter, cfg.ee_cost);
+        return mpc_slot_tables<NX, NU, T>(in_t, out_t, in.b, in.mb, is, b, mb, hs, cfg.N, cfg.M, cfg.A, cfg.max_iter, cfg.ee_cost, table_record_len());
     }
     // pddp_mpc_slots_profile (measurement): HIP events around the in stage (movers + load kernel), the cycle and the out stage of every chunk
     bool slots_timing = false;
@@ -1170,7 +1259,7 @@ struct Solver : SolverBase {
         }
         else if (phase == PDDP_PHASE_BP_COOP) { fs_vars_stale = false; hipLaunchKernelGGL((k_bp<P, T>), dim3(cfg.M, B), dim3(64), 0, stream, b, dm); }
         else if (phase == PDDP_PHASE_INIT_NIS) launch_nis(stream, 1);
-        else if (phase == PDDP_PHASE_INIT_COST) hipLaunchKernelGGL((k_init_cost<P, T>), dim3(B), dim3(64), cfg.N * sizeof(T), stream, b, dm, cw, sp, 1, 0, cfg.ee_cost ? 1 : 0, 0);
+        else if (phase == PDDP_PHASE_INIT_COST) launch_init_cost(stream, 1, 0, cfg.ee_cost ? 1 : 0, 0);
         else return fail(PDDP_EINVAL, "unknown phase");
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));

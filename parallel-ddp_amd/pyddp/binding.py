@@ -332,6 +332,43 @@ class Solver:
         self._chk(self.lib.pddp_get_cost_problems(self.h, idx.size, _p(idx), _p(w)))
         return w
 
+    def has_diag_cost(self):
+        """True for the plants whose cost is a run-time diagonal record (pendulum, cart-pole, quadrotor): set_diag_cost / set_diag_cost_problems / get_diag_cost_problems."""
+        return self.cfg.plant in (1, 2, 3)
+
+    def diag_cost_size(self):
+        """pddp_diag_cost_size: 2 n + m (pendulum 5, cart-pole 9, quadrotor 28) -- the record [q_0..q_{n-1} | r_0..r_{m-1} | qf_0..qf_{n-1}]; plants 1-3 only."""
+        rc = self.lib.pddp_diag_cost_size(self.h)
+        if rc <= 0:
+            self._chk(rc if rc else -1)
+        return rc
+
+    def set_diag_cost(self, w):
+        """pddp_set_diag_cost: one diagonal cost record for every problem of the handle; in force for the following loads and solves."""
+        w = np.ascontiguousarray(w, dtype=np.float64).ravel()
+        if w.size != self.diag_cost_size():
+            raise PddpError(f"set_diag_cost: the record has {self.diag_cost_size()} weights, got {w.size}")
+        self.lib.pddp_set_diag_cost.argtypes = [C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_diag_cost(self.h, _p(w)))
+
+    def set_diag_cost_problems(self, idx, w):
+        """pddp_set_diag_cost_problems: record i of w (len(idx) x diag_cost_size() doubles, any shape) for slot idx[i]; in force for the following loads and solves
+        (follow it with load() or load_problems(idx, ...)); the other slots keep theirs."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        w = np.ascontiguousarray(w, dtype=np.float64).ravel()
+        if w.size != idx.size * self.diag_cost_size():
+            raise PddpError(f"set_diag_cost_problems: {idx.size} slots need {idx.size * self.diag_cost_size()} weights ({self.diag_cost_size()} per record), got {w.size}")
+        self.lib.pddp_set_diag_cost_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_diag_cost_problems(self.h, idx.size, _p(idx), _p(w)))
+
+    def get_diag_cost_problems(self, idx):
+        """pddp_get_diag_cost_problems: [len(idx)][diag_cost_size()] doubles, what the device holds for those slots (the plant's built-in record before any setter call)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        w = np.zeros((idx.size, self.diag_cost_size()), np.float64)
+        self.lib.pddp_get_diag_cost_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_get_diag_cost_problems(self.h, idx.size, _p(idx), _p(w)))
+        return w
+
     def solve(self, x0, u0, xGoal, clear_vars=1, ignore_first_defect=1, max_sweeps=None, chunk=8, **load_kw):
         """load -> iterate until every problem has exited -> store (the shape of runiLQR_GPU)."""
         self.load(x0, u0, xGoal, clear_vars, ignore_first_defect, **load_kw)

@@ -2,7 +2,8 @@
 
 SlotScheduler holds the bookkeeping -- which problem sits in which slot, which slots are padding -- and needs only four methods of a solver: status(), iterate(sweeps),
 load_problems(idx, x0, u0, xGoal, ignore_first_defect) and store_problems(idx), plus load(x0, u0, xGoal) for the first fill; tests drive it with a fake solver on the CPU.
-A stream whose problems carry cost records also needs set_cost_problems(idx, w) and get_cost_problems(idx); a stream of plain (x0, u0, xGoal) never calls them.
+A stream whose problems carry cost records also needs set_cost_problems(idx, w) and get_cost_problems(idx) -- or, on a solver whose has_diag_cost() is true (pendulum,
+cart-pole, quadrotor), set_diag_cost_problems / get_diag_cost_problems; a stream of plain (x0, u0, xGoal) never calls them.
 """
 import numpy as np
 
@@ -10,7 +11,8 @@ import numpy as np
 class SlotScheduler:
     """problems: an iterable of (x0, u0, xGoal), each one problem's arrays ([N][n], [N][m], [n], any shape with those sizes).  run() yields (problem index, result) in the
     order the problems finish; result = that problem's row of store_problems() plus done / iters.
-    A problem may be (x0, u0, xGoal, cost_record): its own cost weights (Solver.set_cost_problems: 5 or 9 numbers), written for its slot immediately before the load
+    A problem may be (x0, u0, xGoal, cost_record): its own cost weights (Solver.set_cost_problems: 5 or 9 numbers of the arm; Solver.set_diag_cost_problems: the diagonal
+    record of the pendulum, cart-pole or quadrotor), written for its slot immediately before the load
     that puts it there.  Once any problem of the stream has carried a record, a problem without one gets the handle-wide record written for its slot -- a slot never
     inherits its previous tenant's weights."""
 
@@ -36,12 +38,15 @@ class SlotScheduler:
 
     def _set_costs(self, slots, probs):
         """the cost records of the problems about to be loaded into `slots` (nothing while the stream has carried none)"""
+        diag = getattr(self.s, "has_diag_cost", None)
+        diag = bool(diag and diag())                               # the diagonal record of plants 1-3, or the arm's record
         if self.wide is None:
             if not any(len(p) > 3 and p[3] is not None for p in probs):
                 return
-            self.wide = np.array(self.s.get_cost_problems([0]), dtype=np.float64).reshape(-1)
+            getter = self.s.get_diag_cost_problems if diag else self.s.get_cost_problems
+            self.wide = np.array(getter([0]), dtype=np.float64).reshape(-1)
         w = np.stack([np.asarray(p[3], dtype=np.float64).reshape(-1) if len(p) > 3 and p[3] is not None else self.wide for p in probs])
-        self.s.set_cost_problems(list(slots), w)
+        (self.s.set_diag_cost_problems if diag else self.s.set_cost_problems)(list(slots), w)
 
     def run(self):
         first = self._draw(self.B)
