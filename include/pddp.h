@@ -30,7 +30,7 @@ extern "C" {
 typedef struct pddp_solver* pddp_handle;
 
 /* Which kernel family a handle uses for each phase of a sweep.  0 everywhere (what pddp_default_config writes) = the library's own choice: one function of plant,
- * element type, batch, M, A and the cost family (Solver::init in csrc/pddp_api.hip; the table is asserted by tests/test_kernel_selection.py and reported back by
+ * element type, batch, M, A and the cost family (make_kernel_plan in csrc/kernel_plan.hpp; the table is asserted by tests/test_kernel_plan.py and tests/test_kernel_selection.py and reported back by
  * pddp_time_kernels).  Every family computes the same functions; the other values exist so that comparison tests and measurements can pin a family WITHOUT the
  * library reading the process environment (until round 4 these were environment variables).  A value that does not apply to the handle's plant is
  * ignored exactly as the variable was. */

@@ -11,6 +11,7 @@
 #include "bp_lg.hpp"
 #include "bp_cl.hpp"
 #include "bp_mq.hpp"
+#include "kernel_plan.hpp"
 #include "mpc.hpp"
 #include "sim.hpp"
 
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(64) void k_bp_ts(Buffers<T> b, Dims dm, int batch) 
     BpScratch<P, T> s;
     bp_body<P, T>(serial_wave(), s, b, dm, inst % dm.M, inst / dm.M);
 }
-constexpr int kTsMaxN = 256, kTsMaxM = 16;        // longest horizon / most segments the thread-serial forward pass keeps per-knot costs / hand-off states for
+// (kTsMaxN / kTsMaxM, the longest horizon / most segments of the thread-serial forward pass: kernel_plan.hpp)
 template <typename P, int INTEG, typename T>
 __global__ __launch_bounds__(64) void k_fp_ts(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int batch, int no_sweep = 0) {
     const int inst = blockIdx.x * 64 + threadIdx.x;

@@ -13,21 +13,6 @@
 
 using namespace pddp;
 
-// (problem, block) pairs from which the matrix-core backward pass is the default for float handles of the arm (profiles/r02_path_sweep_mx.txt)
-static constexpr size_t kBpMfmaMinBlocks = 1;
-// pddp_kernel_selection values by name (0 = nullptr: the library's choice).  The selection logic below is written against these names -- they were the values of the
-// PDDP_BP / PDDP_FP / ... environment variables it read until round 4.
-static const char* ksel(int v, std::initializer_list<const char*> names) { return (v > 0 && (size_t)v <= names.size()) ? *(names.begin() + (v - 1)) : nullptr; }
-static const char* ksel_bp(const pddp_config& c) { return ksel(c.kernels.bp, {"mx", "lg", "coop", "wide"}); }
-static const char* ksel_fp(const pddp_config& c) { return ksel(c.kernels.fp, {"tl", "lg", "coop", "tl2", "tl4"}); }
-static const char* ksel_sweep(const pddp_config& c) { return ksel(c.kernels.sweep, {"alpha", "st", "wg", "maps"}); }
-static const char* ksel_ls(const pddp_config& c) { return ksel(c.kernels.ls, {"many", "wg"}); }
-static const char* ksel_ab(const pddp_config& c) { return ksel(c.kernels.ab, {"full"}); }
-static const char* ksel_cf(const pddp_config& c) { return ksel(c.kernels.cf, {"ts", "coop"}); }
-static const char* ksel_cf_bp(const pddp_config& c) { return ksel(c.kernels.cf_bp, {"ts", "coop", "gl", "gl32", "cl", "mq"}); }
-static const char* ksel_cf_fp(const pddp_config& c) { return ksel(c.kernels.cf_fp, {"ts", "coop", "cf"}); }
-static const char* ksel_cf_nis(const pddp_config& c) { return ksel(c.kernels.cf_nis, {"ts", "coop", "gl", "gl8", "kb16", "kb32", "kb64", "kb20"}); }
-
 template <typename P, int INTEG, typename T>
 struct Solver : SolverBase {
     static constexpr int NX = P::NX, NU = P::NU, NM = NX + NU, NP = P::NPOS;
@@ -43,16 +28,8 @@ struct Solver : SolverBase {
     T dt{};
     std::map<std::string, std::pair<void*, size_t>> arrays;
     std::vector<void*> allocs;
-    // backward pass of the arm: the lane-group kernel carries 8 (problem, block) pairs per wave and wins once the GPU is
-    // full; the wave-cooperative kernel has the shorter critical path for a handful of problems.  PDDP_BP=lg|coop overrides.
-    bool bp_lane_groups = false;
-    bool fp_coop = false;          // PDDP_FP=coop
-    static constexpr int kNisTl7MaxBatch = 511;   // measured crossover against k_nis_lg (profiles/)
-    bool nis_tl7_batch = false;    // batch <= kNisTl7MaxBatch: a split-rollout handle's setup runs on k_nis_tl7 (a resolved choice like the others: the intake area of a large handle keeps the handle's)
-    bool fp_split = false;         // rollouts of a lane-group handle on the split thread-lane kernels (k_fp_tl4 / k_fp_tl2)
-    bool fp_two_wave = false;
-    bool ls_many = false;          // line search one thread per problem (k_ls_many): from 2048 problems in flight
-    FpPath fp_path = kFpLg;        // the arm's forward pass / next-iteration setup (fp_tl.hpp select_fp_path)
+    KernelPlan plan;               // which kernel family runs each phase and which optional arrays they need (kernel_plan.hpp); an intake area holds its handle's
+    void resolve_plan() { plan = make_kernel_plan(cfg, PlantTraits{P::PLANT, NX, NU, P::kScalarPlugin, P::kPluginCost}, sizeof(T) == 4, tl_variant); }
     int tl_variant = -1;           // which built-in robot model the handle's tables equal (the thread-lane kernels fold it into literals); -1: neither
     T tl_grav = T(0);
     void derive_tl_model(const ArmModel<T>& hm) {
@@ -61,19 +38,6 @@ struct Solver : SolverBase {
         if (arm_tl_model_from_tables(m, hm))
             for (int v = 0; v < 2; v++) if (arm_tl_models_equal(m, arm_tl_builtin<T>(v))) tl_variant = v;
         tl_grav = hm.grav;
-        // USE_FINITE_DIFF: the setup runs on the wave-cooperative kernel (k_nis: any plant's `dynamics`), which adopts the winner from the candidate-major
-        // xs / us / ds -- so the rollouts stay on lane groups (they write those), not on the thread-lane kernels
-        fp_path = select_fp_path(ksel_fp(cfg), sizeof(T) == 4, cfg.ee_cost != 0, tl_variant >= 0 && !cfg.use_finite_diff, cfg.batch);
-        if ((cfg.use_limits || cfg.use_smooth_abs) && fp_path == kFpLg) fp_path = kFpCoop;      // USE_LIMITS_FLAG / USE_SMOOTH_ABS: the lane-group family does not carry the variants
-        fp_coop = (fp_path == kFpCoop);
-        // few problems in flight, joint-space cost, float, built-in robot model: the rollouts run on k_fp_tl2 (every step split over two wavefronts);
-        // sweep, line search and setup stay on the lane-group kernels.  PDDP_FP=lg keeps the lane-group rollouts (bit-identity tests), PDDP_FP=tl2 asks for the split.
-        const char* fpenv = ksel_fp(cfg);
-        fp_split = sizeof(T) == 4 && fp_path == kFpLg && !cfg.use_finite_diff && tl_variant >= 0 && !(fpenv && std::string(fpenv) == "lg");
-        // PDDP_FP=tl4 on a DOUBLE handle: the same few-problem selection (k_fp_tl4 pipeline + k_nis_tl7) in its parity instantiation (tests/test_f64_benched_family.py)
-        if (sizeof(T) == 8 && fpenv && std::string(fpenv) == "tl4" && fp_path == kFpLg && !cfg.use_finite_diff && tl_variant >= 0 && !cfg.use_limits && !cfg.use_smooth_abs) fp_split = true;
-        // the split's current form is the four-wave pipeline (k_fp_tl4, fp_pipe.hpp; also the end-effector cost family); PDDP_FP=tl2 keeps the two-wave kernel (joint-space cost only)
-        fp_two_wave = fp_split && !cfg.ee_cost && fpenv && std::string(fpenv) == "tl2";
     }
     void derive_tl_model(const EmptyModel&) {}
     // pddp_set_array("model_I" / "model_F"): re-derive what the kernels take from the model tables as launch arguments
@@ -102,7 +66,7 @@ struct Solver : SolverBase {
     }
     int cand_view(int to_records) override {
         if constexpr (P::PLANT != 4) {
-            if (b.xw && cf_fp_staged) {
+            if (b.xw && plan.cf_fp_staged) {
                 const dim3 g((unsigned)(((size_t)cfg.batch * cfg.N * cfg.A + 255) / 256));
                 if (to_records) hipLaunchKernelGGL((k_cand_to_xw<P, T>), g, dim3(256), 0, stream, b, dm, (int)cfg.batch);
                 else hipLaunchKernelGGL((k_xw_to_cand<P, T>), g, dim3(256), 0, stream, b, dm, (int)cfg.batch);
@@ -124,34 +88,15 @@ struct Solver : SolverBase {
         typename P::Model hm;
         HIPCHK(hipMemcpy(&hm, b.model, sizeof(hm), hipMemcpyDeviceToHost));
         derive_tl_model(hm);
+        resolve_plan();
         drop_graph();
         return 0;
     }
-    bool cf_bp = false, cf_fp = false, cf_nis = false;   // ... per phase
-    bool gl_bp32 = false, gl_nis8 = false;
-    bool cl_bp = false;                                  // 12 states + 4 controls: 16 lanes per block of knots, lane = column (k_bp_cl, bp_cl.hpp) instead of k_bp_gl; PDDP_CF_BP = cl | gl | gl32
-    bool mq_bp = false;                                  // 12 states + 4 controls on the matrix cores (k_bp_mq, bp_mq.hpp): where k_bp_cl was the choice, for the plant's own diagonal cost Hessian; kernels.cf_bp = mq | cl
-    bool mq_fused = false;                               // k_bp_mq composes the segments' forward-sweep maps itself (bp_mq.hpp FUSE) and k_sweep_maps_cf finishes: no A - B K / B du traffic, no per-knot sweep; kernels.sweep = st: k_sweep_cf
-    bool cf_fp_staged = false;                           // thread-serial rollouts with the knot's operands staged through LDS once per wavefront (k_fp_cf: 16 step sizes, 12-state plants); PDDP_CF_FP = cf | ts
-    int kb_nis = 0;                                      // knots per wavefront of the knot-batched setup kernel (k_nis_kb: scalar plug-ins, RK3); 0 = k_nis_gl.  PDDP_CF_NIS = kb16 | kb32 | kb64
-    bool gl_bp = false, gl_nis = false;                  // 16 lanes per unit (k_bp_gl / k_nis_gl): the 12-state plants with the device full; PDDP_CF_BP / _NIS = gl
-    bool cf_serial = false;        // closed-form plants with many problems in flight: thread-serial kernels (k_bp_ts / k_fp_ts / k_nis_ts); PDDP_CF=coop|ts overrides
-    bool bp_wide = false;          // cooperative backward pass with a whole workgroup per block of knots (few problems in flight); PDDP_BP=wide
     bool phase_fused_sweep = false; // pddp_run_phase(PDDP_PHASE_BP_FUSED / _SWEEP_FUSED): the teacher-forcing hook runs the production sweep path (maps composed in the backward pass)
-    bool sweep_fused = false;      // production sweeps: forward-sweep maps composed inside k_bp_mfma + k_sweep_maps (no A - B K / B du traffic)
-    int sweep_kind = 0;            // the arm's linear sweep: 0 one lane group per candidate (k_sweep_lg), 1 two sequences on lane groups (k_sweep_st), 2 two sequences, workgroup per problem (k_sweep_wg); PDDP_SWEEP=alpha|st|wg
     bool mpc_used = false;         // pddp_mpc_solve ran on this handle: its warm start shifts every cost-to-go slot, so the backward pass keeps writing all of them
     bool lean_ctg_ran = false;     // sweeps ran that left the interior cost-to-go slots unwritten (config.boundary_cost_to_go_only): a warm-started MPC call would shift stale slots
     // every knot's P, p written (the reference's d_P / d_p) unless the caller opted out; MPC handles always keep them (MPCHelpers.cuh:602-655 shifts the whole arrays)
     bool keep_all_ctg() const { return !cfg.boundary_cost_to_go_only || cfg.mpc_mode || mpc_used; }
-    bool bp_mfma = false;          // matrix-core backward pass, one wavefront per block of knots (bp_mfma.hpp): float handles of the arm; PDDP_BP=mx
-    // few problems in flight on the four-wave rollout pipeline, every problem's M x A rollouts inside one wavefront: the rollout kernel ends with the line search (k_fp_tl4)
-    bool ls_in_rollouts() const { return P::PLANT == 4 && fp_split && !fp_two_wave && !ls_many && cfg.kernels.ls == 0 && 64 % (cfg.M * cfg.A) == 0; }
-    // ... and BEGINS with the linear forward sweep: the segment maps the backward pass composed are applied in the rollout kernel's prologue (a problem's M x A lanes sit in
-    // one wavefront, 14 of them walk the maps) instead of by a k_sweep_maps launch in front of it -- one more kernel boundary of the ~115 us iteration gone.
-    // kernels.sweep = maps keeps the separate kernel (A/B, tests); so do the phase hooks and the per-phase / per-kernel timing, which launch the sweep on its own.
-    bool cf_records() const { return P::PLANT != 4 && cf_fp && cf_fp_staged; }      // production rollouts = k_sweep_cf + k_fp_cf (records in xw)
-    bool maps_in_rollouts() const { return P::PLANT == 4 && sweep_fused && cfg.kernels.sweep == 0 && fp_split && !fp_two_wave && 64 % (cfg.M * cfg.A) == 0 && cfg.M * cfg.A >= 16; }
     hipGraphExec_t graph = nullptr;
     int graph_mode = -1;
     size_t fp_lds = 0;
@@ -203,58 +148,6 @@ struct Solver : SolverBase {
         else HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         dm.N = c.N; dm.M = c.M; dm.A = c.A; dm.NB = c.N / c.M;
         cap_batch = c.batch;
-        nis_tl7_batch = c.batch <= kNisTl7MaxBatch;
-        bp_lane_groups = (size_t)c.batch * c.M >= 4096;     // measured crossovers on MI355X (Kuka N=128): wide <= 256 problems < cooperative < 1024 <= lane groups
-        bp_wide = (size_t)c.batch * c.M <= 1024 && P::NX >= 12;
-        if (const char* v = ksel_fp(cfg)) fp_coop = (std::string(v) == "coop");       // the arm refines this below (derive_tl_model)
-        // closed-form plants (and user plants): one wave per unit while a handful of problems is in flight (the shorter critical path), one thread per unit once
-        // the batch fills the device (64 units per wave instead of 1); the horizon has to fit the per-thread cost table of k_fp_ts
-        { const char* e = ksel_ls(cfg); ls_many = e ? std::string(e) == "many" : c.batch >= 2048; }      // PDDP_LS=many|wg
-        cf_serial = P::PLANT != 4 && (size_t)c.batch * c.M >= 256 && c.N <= kTsMaxN && c.M <= kTsMaxM;
-        if (const char* v = ksel_cf(cfg)) cf_serial = P::PLANT != 4 && std::string(v) == "ts" && c.N <= kTsMaxN && c.M <= kTsMaxM;
-        // measured on MI355X (tools/cf_variants.py; profiles/r03_closed_form_variants.txt): the rollouts always win thread-serially once the device is full (cart-pole, 16384
-        // problems: 0.74 against 15.7 ms; quadrotor, 4096: 3.0 against 57.9 ms); the derivative kernel too for the small plants (0.16 against 2.1 ms) but not for the
-        // quadrotor's 12 states, whose per-thread stage scratch spills to memory (6.2 against 5.4 ms); the backward pass thread-serially only for the small plants with the
-        // device full (0.42 against 0.65 ms; quadrotor: its 64-knot serial chain on private memory takes 15 ms against 1.9 ms for a wave per block)
-        cf_fp = cf_serial;
-        cf_nis = cf_serial && P::NX < 12;
-        cf_bp = cf_serial && P::NX < 12 && (size_t)c.batch * c.M >= 8192;
-        if (ksel_cf(cfg)) cf_bp = cf_nis = cf_fp;         // the override forces every phase
-        // per-phase overrides (measurement): PDDP_CF_BP / PDDP_CF_FP / PDDP_CF_NIS = coop | ts
-        if (const char* v = ksel_cf_bp(cfg)) cf_bp = P::PLANT != 4 && std::string(v) == "ts";
-        if (const char* v = ksel_cf_fp(cfg)) cf_fp = P::PLANT != 4 && std::string(v) == "ts" && c.N <= kTsMaxN && c.M <= kTsMaxM;
-        if (const char* v = ksel_cf_nis(cfg)) cf_nis = P::PLANT != 4 && std::string(v) == "ts";
-        gl_nis = cf_serial && !cf_nis && P::NX + P::NU <= 16 && !ksel_cf(cfg);
-        gl_bp = cf_serial && !cf_bp && P::NX + P::NU <= 16 && (size_t)c.batch * c.M >= 8192 && !ksel_cf(cfg); gl_bp32 = true;      // 32 lanes per block of knots: 1.92 -> 1.72 ms (quadrotor, 4096 problems); 16 lanes: 2.5 ms
-        if (const char* v = ksel_cf_nis(cfg)) { gl_nis = P::PLANT != 4 && (std::string(v) == "gl" || std::string(v) == "gl8") && P::NX + P::NU <= 16; gl_nis8 = std::string(v) == "gl8"; }
-        cl_bp = gl_bp && P::NX == 12 && P::NU == 4;
-        mq_bp = cl_bp;                                                    // round 5: 4.1 -> ... ms at 16384 quadrotor problems (profiles/r05_quad_mfma.md)
-        const bool cf_fits = (c.A == 16 && (64 / 16) * P::NX <= 64) || (c.A == 8 && (64 / 8) * P::NX <= 64);      // whole problems per wavefront, one state fetch per lane
-        cf_fp_staged = cf_fp && cf_fits && !ksel_cf(cfg);      // (cart-pole, 16384 problems: 0.73 -> 0.69 ms; quadrotor: 8.6 -> 5.1 ms)
-        if (const char* v = ksel_cf_fp(cfg)) { if (std::string(v) == "cf") { cf_fp = P::PLANT != 4 && c.N <= kTsMaxN && c.M <= kTsMaxM; cf_fp_staged = cf_fp && cf_fits; } else cf_fp_staged = false; }
-        kb_nis = (gl_nis && c.integrator == 3) ? 16 : 0;      // 16 knots per wavefront: 2.15 ms (32: 2.6, 64: 3.6; the 16-lane-group kernel 5.7-7.1) at 16384 quadrotor problems -- LDS per block sets the occupancy
-        if (const char* v = ksel_cf_nis(cfg)) { const std::string m(v); kb_nis = (P::PLANT != 4 && P::NX + P::NU <= 16 && c.integrator == 3) ? (m == "kb16" ? 16 : m == "kb20" ? 20 : m == "kb32" ? 32 : m == "kb64" ? 64 : 0) : 0; if (kb_nis) { gl_nis = true; cf_nis = false; } }
-        if (const char* v = ksel_cf_bp(cfg)) {
-            const std::string m(v);
-            const bool col = (m == "cl" || m == "mq") && P::NX == 12 && P::NU == 4;
-            gl_bp = P::PLANT != 4 && (m == "gl" || m == "gl32" || col) && P::NX + P::NU <= 16; gl_bp32 = m == "gl32"; cl_bp = gl_bp && col; mq_bp = cl_bp && m == "mq";
-        }
-        // the matrix-core backward pass of the 12-state plants with the record rollouts behind it: fused sweep maps by default (round 6: profiles/r06_quad.md)
-        if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4 && P::kScalarPlugin) {
-            mq_fused = gl_bp && cl_bp && mq_bp && !cf_bp && cf_fp && cf_fp_staged && c.M > 1 && (!ksel_sweep(cfg) || std::string(ksel_sweep(cfg)) == "maps");
-        }
-        if (P::PLANT == 4 && sizeof(T) == 4) {        // float handles of the arm: measured crossover (profiles/r02b_sweep_wg.txt): the staged workgroup sweep up to 512 problems
-            sweep_kind = (c.batch <= 512 && c.N / c.M <= 96) ? 2 : 1;      // (a segment has to fit the 96-knot staging area of k_sweep_wg)
-            if (const char* v = ksel_sweep(cfg)) sweep_kind = std::string(v) == "alpha" ? 0 : std::string(v) == "st" ? 1 : std::string(v) == "wg" ? 2 : sweep_kind;
-            if (sweep_kind == 2 && c.N / c.M > 96) sweep_kind = 1;
-            // default with the matrix-core backward pass: that pass composes the segments' sweep maps itself (bp_mfma.hpp kMxFuseSweep) and k_sweep_maps finishes;
-            // sweep_kind stays the kernel of the phase hook, whose teacher-forced A - B K / B du must be what the sweep reads.  PDDP_SWEEP=alpha|st|wg: no fusion.
-        }
-        bp_mfma = (P::PLANT == 4 && sizeof(T) == 4 && (size_t)c.batch * c.M >= kBpMfmaMinBlocks);
-        // PDDP_BP=mx on a double handle: the same tile algebra on v_mfma_f64_16x16x4_f64 (a test selection: float64 handles default to the lane-group family,
-        // whose operation order is the reference's)
-        if (const char* v = ksel_bp(cfg)) { bp_lane_groups = (std::string(v) == "lg"); bp_wide = (std::string(v) == "wide"); bp_mfma = (P::PLANT == 4 && std::string(v) == "mx"); }
-        sweep_fused = bp_mfma && c.M > 1 && (!ksel_sweep(cfg) || std::string(ksel_sweep(cfg)) == "maps");
         sp = solver_params_of(c); cw = cost_weights_of<T, P::PLANT>(c); dt = time_step<T>(c);
         const size_t B = c.batch, N = c.N, A = c.A, M = c.M;
         int rc = for_each_array<NX, NU>(c, b, mb, arrays, [this](const char* name, auto** out, size_t count) { return alloc(name, out, count); });
@@ -273,20 +166,11 @@ struct Solver : SolverBase {
         b.model = dmodel;
         register_model(dmodel, hm);
         derive_tl_model(hm);
-        if (intake_of) adopt_selection(*intake_of);      // before the arrays below that exist only on some kernel families
-        if constexpr (P::PLANT != 4) { if (cf_fp_staged) { b.xw_rec = P::NX + P::NU; if ((rc = alloc("xw", &b.xw, B * N * A * b.xw_rec))) return rc; } }   // records of the staged closed-form rollouts (k_fp_cf)
-        if constexpr (P::PLANT == 4) { if (fp_path == kFpTl) { b.xw_rec = 22; if ((rc = alloc("xw", &b.xw, B * N * A * b.xw_rec))) return rc; } }   // knot-major candidate states (fp_tl.hpp)
-        if constexpr (P::PLANT == 4) { if (sweep_fused) { if ((rc = alloc("segmap", &b.segmap, B * M * 256))) return rc; } }
-        if (mq_fused) { if ((rc = alloc("segmap", &b.segmap, B * M * 256))) return rc; }
-        if constexpr (P::PLANT == 4) {
-            const char* abenv = ksel_ab(cfg);             // PDDP_AB=full: keep the reference layout (comparison runs)
-            const bool full_h = c.ee_cost && c.use_limits;         // end-effector cost with USE_LIMITS_FLAG: the whole diagonal of H moves with the trajectory -> reference-layout H and [A B]
-            if (bp_mfma && fp_path == kFpTl && !(abenv && abenv[0] == 'f') && !full_h) {
-                if ((rc = alloc("ABc", &b.ABc, abc_floats(B * N)))) return rc;
-                // end-effector cost: the Gauss-Newton Hessian's only dense part, the 7 x 7 position block, travels compact as well (bp_mfma.hpp HQQ)
-                if (c.ee_cost) { if ((rc = alloc("Hc", &b.Hc, B * N * 49 + 16))) return rc; }
-            }
-        }
+        if (intake_of) adopt_selection(*intake_of); else resolve_plan();      // before the arrays below that exist only on some kernel families
+        if (plan.xw_rec) { b.xw_rec = plan.xw_rec; if ((rc = alloc("xw", &b.xw, B * N * A * b.xw_rec))) return rc; }   // candidate records: staged closed-form rollouts (k_fp_cf), knot-major states of the thread-lane arm (fp_tl.hpp)
+        if (plan.segmap) { if ((rc = alloc("segmap", &b.segmap, B * M * 256))) return rc; }
+        if (plan.ab_compact) { if ((rc = alloc("ABc", &b.ABc, abc_floats(B * N)))) return rc; }
+        if (plan.h_compact) { if ((rc = alloc("Hc", &b.Hc, B * N * 49 + 16))) return rc; }
         // device tables of per-alpha pointers, the reference's d_x / d_u / d_d (nisInitHelpers.cuh:777-789,808-813)
         void** tab[3]; const char* tn[3] = {"xs_ptrs", "us_ptrs", "ds_ptrs"};
         T* base[3] = {b.xs, b.us, b.ds}; const size_t per[3] = {N * NX, N * NU, N * NX};
@@ -308,8 +192,7 @@ struct Solver : SolverBase {
                 for (const void* k : ks) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             }
         }
-        const bool uses_coop_fp = (P::PLANT != 4) || fp_coop || cfg.use_limits || cfg.use_smooth_abs;      // the arm's forward pass runs on lane groups (no per-segment LDS scratch) unless PDDP_FP=coop
-        if (uses_coop_fp) {
+        if (plan.fp_coop_lds) {
             if (fp_lds > 160 * 1024) return fail(PDDP_EINVAL, "forward-pass LDS footprint exceeds 160 KiB: reduce M");
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fp<P, INTEG, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp_lds));
         }
@@ -374,19 +257,19 @@ struct Solver : SolverBase {
     // themselves still do); 2 the rollouts WITHOUT any sweep, from the start states in xs (PDDP_PHASE_ROLLOUT)
     bool launch_sweep_maps_cf(hipStream_t s) {                // the record rollouts' sweep from the maps the fused matrix-core backward pass left (false: not this handle's path)
         if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4) {
-            if (mq_fused) { hipLaunchKernelGGL((k_sweep_maps_cf<P, T>), dim3((cfg.batch + 3) / 4), dim3(64), 0, s, b, dm, (int)cfg.batch); return true; }
+            if (plan.mq_fused) { hipLaunchKernelGGL((k_sweep_maps_cf<P, T>), dim3((cfg.batch + 3) / 4), dim3(64), 0, s, b, dm, (int)cfg.batch); return true; }
         }
         return false;
     }
     void launch_fp(hipStream_t s, int init_rollout, int store_candidates = 0, int part = -1) {
         const unsigned B = cfg.batch;
         bool lane_groups = false;
-        if constexpr (P::PLANT == 4) lane_groups = !fp_coop && !(init_rollout && (cfg.use_limits || cfg.use_smooth_abs));       // PDDP_FP=coop: the wave-cooperative forward pass / setup kernels (comparison tests); the initial rollout of a thread-lane handle with USE_LIMITS_FLAG too
+        if constexpr (P::PLANT == 4) lane_groups = !plan.fp_coop && !(init_rollout && (cfg.use_limits || cfg.use_smooth_abs));       // PDDP_FP=coop: the wave-cooperative forward pass / setup kernels (comparison tests); the initial rollout of a thread-lane handle with USE_LIMITS_FLAG too
         if (!lane_groups) {
             bool serial = false, records_ran = false;
             if constexpr (P::PLANT != 4) {      // (the arm has its own families: no thread-serial instantiation of its cooperative bodies)
                 if (phase_fused_sweep && part == 0) { launch_sweep_maps_cf(s); return; }      // PDDP_PHASE_SWEEP_FUSED: the candidates' segment start states land in their records (xw)
-                const bool records = cf_fp && cf_fp_staged && !init_rollout && part != 2 && !store_candidates;      // (the phase hook wants the reference's candidate-major arrays: k_fp_ts, then k_cand_to_xw)
+                const bool records = plan.cf_fp && plan.cf_fp_staged && !init_rollout && part != 2 && !store_candidates;      // (the phase hook wants the reference's candidate-major arrays: k_fp_ts, then k_cand_to_xw)
                 if (records) cand_stale = true;
                 // two launches: the linear sweep (segment start states -> the candidates' records), then the rollouts (kernels.hpp fp_cf_body); part 0 / 1 = only the one / the other
                 if constexpr (P::kScalarPlugin && (64 / 16) * P::NX <= 64) {
@@ -404,7 +287,7 @@ struct Solver : SolverBase {
                     }
                 }
                 if (part == 0) return;                                  // (the paths below sweep inside their rollout kernel)
-                if (!serial && cf_fp && !init_rollout) { with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, part == 2 ? 1 : 0); }); serial = true; }
+                if (!serial && plan.cf_fp && !init_rollout) { with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, part == 2 ? 1 : 0); }); serial = true; }
             }
             if (part == 0) return;
             if (!serial) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(init_rollout ? 1 : cfg.A, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, init_rollout ? 1 : (part == 2 ? 2 : 0)); });
@@ -418,25 +301,25 @@ struct Solver : SolverBase {
             const unsigned waves = (A_eff * cfg.M + kLgPerWave - 1) / kLgPerWave;
             if (!init_rollout && cfg.M > 1 && part != 1 && part != 2) {
                 bool st = false;
-                const bool in_rollouts = maps_in_rollouts() && part == -1 && !store_candidates;      // (k_fp_tl4 begins with the sweep)
+                const bool in_rollouts = plan.maps_in_rollouts && part == -1 && !store_candidates;      // (k_fp_tl4 begins with the sweep)
                 if (in_rollouts) st = true;
-                else if (sweep_fused && (!store_candidates || phase_fused_sweep)) { launch_sweep_maps<T>(s, b, dm, (int)B); st = true; }
+                else if (plan.sweep_fused && (!store_candidates || phase_fused_sweep)) { launch_sweep_maps<T>(s, b, dm, (int)B); st = true; }
                 if constexpr (sizeof(T) == 4) {
                     if (st) {}
-                    else if (sweep_kind == 2) { launch_sweep_wg(s, b, dm, (int)B); st = true; }
-                    else if (sweep_kind == 1) { launch_sweep_st(s, b, dm, (int)B); st = true; }
+                    else if (plan.sweep_kind == 2) { launch_sweep_wg(s, b, dm, (int)B); st = true; }
+                    else if (plan.sweep_kind == 1) { launch_sweep_st(s, b, dm, (int)B); st = true; }
                 }
                 if (!st) hipLaunchKernelGGL((k_sweep_lg<T>), dim3((cfg.A + kLgPerWave - 1) / kLgPerWave, B), dim3(64), 0, s, b, dm, dt);
             }
             if (part == 0) return;
-            if (!init_rollout && fp_split) {
+            if (!init_rollout && plan.fp_split) {
                 bool two = false;
-                if constexpr (sizeof(T) == 4) { if (fp_two_wave) { launch_fp_tl2(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B); two = true; } }
-                if (!two) launch_fp_tl4<T>(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B, sp, (ls_in_rollouts() && !store_candidates && part != 2) ? bench_mode : -1,
-                                           maps_in_rollouts() && part == -1 && !store_candidates);
+                if constexpr (sizeof(T) == 4) { if (plan.fp_two_wave) { launch_fp_tl2(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B); two = true; } }
+                if (!two) launch_fp_tl4<T>(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B, sp, (plan.ls_in_rollouts && !store_candidates && part != 2) ? bench_mode : -1,
+                                           plan.maps_in_rollouts && part == -1 && !store_candidates);
                 return;
             }
-            if (!init_rollout && fp_path == kFpTl) {               // one thread per (candidate, segment) rollout
+            if (!init_rollout && plan.fp_path == kFpTl) {               // one thread per (candidate, segment) rollout
                 launch_fp_tl<T>(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B, store_candidates);
                 return;
             }
@@ -460,95 +343,113 @@ struct Solver : SolverBase {
     void note_setup_weights() { const bool ee = cfg.ee_cost != 0; hw[0] = ee ? cw.Q_xEE : cw.Q1; hw[1] = ee ? cw.Q_xdEE : cw.Q2; hw[2] = ee ? cw.R_EE : cw.R; }
     void launch_nis(hipStream_t s, int mode, int part = -1) {
         const unsigned B = cfg.batch;
-        if (part != 0) note_setup_weights();
-        if constexpr (P::PLANT == 4) {
-            if (fp_path == kFpTl) {
-                if (part != 0) launch_nis_tl<T>(s, tl_variant, b, dm, cw, dt, tl_grav, mode, (int)B);   // mode 0: adopts the accepted candidate first (arm_tl_adopt_knot)
-                return;
-            }
-            if (!fp_coop && !cfg.use_finite_diff) {
-                if (part == 0) return;
-                if (fp_split && nis_tl7_batch) { launch_nis_tl7<T>(s, tl_variant, b, dm, cw, dt, tl_grav, mode, (int)B); return; }
+        if (part == 0) return;
+        note_setup_weights();
+        switch (plan.nis) {
+        case kNisTl:                  // mode 0: adopts the accepted candidate first (arm_tl_adopt_knot)
+            if constexpr (P::PLANT == 4) launch_nis_tl<T>(s, tl_variant, b, dm, cw, dt, tl_grav, mode, (int)B);
+            break;
+        case kNisTl7:
+            if constexpr (P::PLANT == 4) launch_nis_tl7<T>(s, tl_variant, b, dm, cw, dt, tl_grav, mode, (int)B);
+            break;
+        case kNisLg:
+            if constexpr (P::PLANT == 4) {
                 if (cfg.ee_cost) hipLaunchKernelGGL((k_nis_lg<T, true>), dim3((cfg.N + 31) / 32, B), dim3(256), 0, s, b, dm, cw, dt, mode);
                 else hipLaunchKernelGGL((k_nis_lg<T>), dim3((cfg.N + 31) / 32, B), dim3(256), 0, s, b, dm, cw, dt, mode);
-                return;
             }
-        }
-        if (part == 0) return;
-        if constexpr (P::PLANT != 4) { if (cf_nis) { with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis_ts<Q, INTEG, T>), dim3((B * cfg.N + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); }); return; } }
-        if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16 && INTEG == 3 && P::kScalarPlugin) {
-            if (gl_nis && kb_nis) {
+            break;
+        case kNisTs:
+            if constexpr (P::PLANT != 4) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis_ts<Q, INTEG, T>), dim3((B * cfg.N + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); });
+            break;
+        case kNisKb:
+            if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16 && INTEG == 3 && P::kScalarPlugin) {
                 const int units = (int)(B * cfg.N);
                 with_cost_plant([&](auto pl) {
                     using Q = decltype(pl);
-                    if (kb_nis == 16) hipLaunchKernelGGL((k_nis_kb<Q, T, 16>), dim3((units + 15) / 16), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
-                    else if (kb_nis == 20) hipLaunchKernelGGL((k_nis_kb<Q, T, 20>), dim3((units + 19) / 20), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
-                    else if (kb_nis == 64 && sizeof(T) == 4) hipLaunchKernelGGL((k_nis_kb<Q, T, sizeof(T) == 4 ? 64 : 16>), dim3((units + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                    if (plan.kb_nis == 16) hipLaunchKernelGGL((k_nis_kb<Q, T, 16>), dim3((units + 15) / 16), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                    else if (plan.kb_nis == 20) hipLaunchKernelGGL((k_nis_kb<Q, T, 20>), dim3((units + 19) / 20), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                    else if (plan.kb_nis == 64 && sizeof(T) == 4) hipLaunchKernelGGL((k_nis_kb<Q, T, sizeof(T) == 4 ? 64 : 16>), dim3((units + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
                     else hipLaunchKernelGGL((k_nis_kb<Q, T, 32>), dim3((units + 31) / 32), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
                 });
-                return;
             }
+            break;
+        case kNisGl:
+            if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) {
+                with_cost_plant([&](auto pl) {
+                    using Q = decltype(pl);
+                    if (plan.gl_nis8) hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 8>), dim3((B * cfg.N + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                    else hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 16>), dim3((B * cfg.N + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
+                });
+            }
+            break;
+        case kNisCoop:
+            if constexpr (P::PLANT == 4) { if (b.cwt) { hipLaunchKernelGGL((k_nis<P, INTEG, T, true>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); break; } }
+            with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis<Q, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); });
+            break;
         }
-        if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) { if (gl_nis) { with_cost_plant([&](auto pl) { using Q = decltype(pl); if (gl_nis8) hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 8>), dim3((B * cfg.N + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); else hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 16>), dim3((B * cfg.N + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); }); return; } }
-        if constexpr (P::PLANT == 4) { if (b.cwt) { hipLaunchKernelGGL((k_nis<P, INTEG, T, true>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); return; } }
-        with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis<Q, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); });
+    }
+    void launch_bp(hipStream_t s, int store_candidates) {
+        const unsigned B = cfg.batch;
+        switch (plan.bp) {
+        case kBpMfma:
+            if constexpr (P::PLANT == 4) {
+                // the running knots' cost Hessian is known without reading it: the joint-space cost's diagonal, or (end-effector cost on the compact path) the diagonal of
+                // the nominal-state / control weights + the compact position block b.Hc
+                const bool ee = cfg.ee_cost != 0;
+                const bool diag_h = !h_overridden && (!ee || b.Hc != nullptr);
+                launch_bp_mfma<T>(s, b, dm, (int)B, diag_h, hw[0], hw[1], hw[2], dt, keep_all_ctg() || store_candidates,
+                                  plan.sweep_fused && (!store_candidates || phase_fused_sweep), ee ? 1 : 0);      // (per-problem weights: the diagonal comes from the table, not from hw)
+            }
+            break;
+        case kBpLg:
+            if constexpr (P::PLANT == 4) hipLaunchKernelGGL((k_bp_lg<T>), dim3((B * cfg.M + kLgPerWave - 1) / kLgPerWave), dim3(64), 0, s, b, dm, (int)B);
+            break;
+        case kBpTs:
+            if constexpr (P::PLANT != 4) hipLaunchKernelGGL((k_bp_ts<P, T>), dim3((B * cfg.M + 63) / 64), dim3(64), 0, s, b, dm, (int)B);
+            break;
+        case kBpMq:
+            if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4) {
+                const bool fu = plan.mq_fused && (!store_candidates || phase_fused_sweep);      // (the phase hook's backward pass writes A - B K / B du: its sweep is teacher-forced from them)
+                const bool dh = !P::kPluginCost && !h_overridden;   // the plant's own diagonal cost Hessian: not read
+                // (only the instantiations that take the running knots' Hessian from the weights differ with a table of diagonal records: the others read H)
+                if (dh && fu) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
+                else if (dh) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
+                else if (fu) hipLaunchKernelGGL((k_bp_mq<P, T, false, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
+                else hipLaunchKernelGGL((k_bp_mq<P, T, false>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
+            }
+            break;
+        case kBpCl:
+            if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4)
+                with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_cl<Q, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, cw, (int)B, (!P::kPluginCost && !h_overridden) ? 1 : 0); });
+            break;
+        case kBpGl:
+            if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) {
+                if (plan.gl_bp32) hipLaunchKernelGGL((k_bp_gl<P, T, 32>), dim3((B * cfg.M + 1) / 2), dim3(64), 0, s, b, dm, (int)B);
+                else hipLaunchKernelGGL((k_bp_gl<P, T, 16>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, (int)B);
+            }
+            break;
+        case kBpWide: hipLaunchKernelGGL((k_bp_wide<P, T>), dim3(cfg.M, B), dim3(256), 0, s, b, dm); break;
+        case kBpCoop: hipLaunchKernelGGL((k_bp<P, T>), dim3(cfg.M, B), dim3(64), 0, s, b, dm); break;
+        }
     }
     void launch_sweep(hipStream_t s, int only = -1, int store_candidates = 0, int part = -1) {
         const unsigned B = cfg.batch;
-        if (only < 0 || only == PDDP_PHASE_BP) {
-            bool lane_groups = false;
-            if constexpr (P::PLANT == 4) lane_groups = bp_lane_groups || bp_mfma;
-            if constexpr (P::PLANT == 4) {
-                if (bp_mfma) {
-                    // the running knots' cost Hessian is known without reading it: the joint-space cost's diagonal, or (end-effector cost on the compact path) the diagonal of
-                    // the nominal-state / control weights + the compact position block b.Hc
-                    const bool ee = cfg.ee_cost != 0;
-                    const bool diag_h = !h_overridden && (!ee || b.Hc != nullptr);
-                    launch_bp_mfma<T>(s, b, dm, (int)B, diag_h, hw[0], hw[1], hw[2], dt, keep_all_ctg() || store_candidates,
-                                      sweep_fused && (!store_candidates || phase_fused_sweep), ee ? 1 : 0);      // (per-problem weights: the diagonal comes from the table, not from hw)
-                }
-            }
-            if constexpr (P::PLANT == 4) { if (lane_groups && !bp_mfma) hipLaunchKernelGGL((k_bp_lg<T>), dim3((B * cfg.M + kLgPerWave - 1) / kLgPerWave), dim3(64), 0, s, b, dm, (int)B); }
-            if (!lane_groups) {
-                bool serial = false;
-                if constexpr (P::PLANT != 4) { if (cf_bp) { hipLaunchKernelGGL((k_bp_ts<P, T>), dim3((B * cfg.M + 63) / 64), dim3(64), 0, s, b, dm, (int)B); serial = true; } }
-                if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4) {
-                    if (!serial && gl_bp && cl_bp && mq_bp) {
-                        const bool fu = mq_fused && (!store_candidates || phase_fused_sweep);      // (the phase hook's backward pass writes A - B K / B du: its sweep is teacher-forced from them)
-                        const bool dh = !P::kPluginCost && !h_overridden;   // the plant's own diagonal cost Hessian: not read
-                        // (only the instantiations that take the running knots' Hessian from the weights differ with a table of diagonal records: the others read H)
-                        if (dh && fu) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
-                        else if (dh) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
-                        else if (fu) hipLaunchKernelGGL((k_bp_mq<P, T, false, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
-                        else hipLaunchKernelGGL((k_bp_mq<P, T, false>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
-                        serial = true;
-                    }
-                }
-                if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4) {
-                    if (!serial && gl_bp && cl_bp) { with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_cl<Q, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, cw, (int)B, (!P::kPluginCost && !h_overridden) ? 1 : 0); }); serial = true; }
-                }
-                if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) { if (!serial && gl_bp) { if (gl_bp32) hipLaunchKernelGGL((k_bp_gl<P, T, 32>), dim3((B * cfg.M + 1) / 2), dim3(64), 0, s, b, dm, (int)B); else hipLaunchKernelGGL((k_bp_gl<P, T, 16>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, (int)B); serial = true; } }
-                if (serial) {}
-                else if (bp_wide) hipLaunchKernelGGL((k_bp_wide<P, T>), dim3(cfg.M, B), dim3(256), 0, s, b, dm);
-                else hipLaunchKernelGGL((k_bp<P, T>), dim3(cfg.M, B), dim3(64), 0, s, b, dm);
-            }
-        }
+        if (only < 0 || only == PDDP_PHASE_BP) launch_bp(s, store_candidates);
         if (only < 0 || only == PDDP_PHASE_FP) launch_fp(s, 0, store_candidates, part);
-        if ((only < 0 || only == PDDP_PHASE_LS) && !(ls_in_rollouts() && !store_candidates)) {      // (k_fp_tl4 ended with the line search of its problems)
-            if (ls_many) hipLaunchKernelGGL((k_ls_many<T>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, b, dm, sp, bench_mode, (int)B);
+        if ((only < 0 || only == PDDP_PHASE_LS) && !(plan.ls_in_rollouts && !store_candidates)) {      // (k_fp_tl4 ended with the line search of its problems)
+            if (plan.ls_many) hipLaunchKernelGGL((k_ls_many<T>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, b, dm, sp, bench_mode, (int)B);
             else hipLaunchKernelGGL((k_ls<T>), dim3(B), dim3(64), 0, s, b, dm, sp, bench_mode);
         }
         if (only < 0 || only == PDDP_PHASE_NIS) launch_nis(s, 0, part);
     }
     // The kernels of one sweep in launch order, by name, and their average duration over `sweeps` sweeps (an event after every launch, one pass).
     // Slots: 0 backward pass, 1 linear sweep, 2 rollouts, 3 line search, 4 winner re-roll, 5 next-iteration setup; a path without a separate kernel
-    // for a slot leaves its name empty and its time 0.
+    // for a slot leaves its name empty and its time 0 (kernel_plan.hpp plan_kernel_names: the names of the enums launch_bp / launch_nis switch over).
     int time_kernels(int sweeps, float* ms, char* names, int name_stride) override {
-        const bool arm = (P::PLANT == 4), tl = arm && fp_path == kFpTl, lg = arm && !fp_coop;
-        const char* nm[6] = {bp_mfma ? "k_bp_mfma" : (arm && bp_lane_groups) ? "k_bp_lg" : cf_bp ? "k_bp_ts" : (gl_bp && cl_bp && mq_bp) ? "k_bp_mq" : (gl_bp && cl_bp) ? "k_bp_cl" : gl_bp ? "k_bp_gl" : bp_wide ? "k_bp_wide" : "k_bp",
-                             (lg && cfg.M > 1 && !maps_in_rollouts()) ? (sweep_fused ? "k_sweep_maps" : sweep_kind == 2 ? "k_sweep_wg" : sweep_kind == 1 ? "k_sweep_st" : "k_sweep_lg") : (cf_records() && cfg.M > 1) ? (mq_fused ? "k_sweep_maps" : "k_sweep_cf") : "", tl ? "k_fp_tl" : (lg && fp_split) ? (fp_two_wave ? "k_fp_tl2" : "k_fp_tl4") : lg ? "k_fp_lg" : (cf_fp && cf_fp_staged) ? "k_fp_cf" : cf_fp ? "k_fp_ts" : "k_fp", ls_in_rollouts() ? "" : ls_many ? "k_ls_many" : "k_ls", "", tl ? "k_nis_tl" : (lg && fp_split && nis_tl7_batch) ? "k_nis_tl7" : lg ? "k_nis_lg" : cf_nis ? "k_nis_ts" : (gl_nis && kb_nis) ? "k_nis_kb" : gl_nis ? "k_nis_gl" : "k_nis"};
+        const char* nm[6];
+        plan_kernel_names(plan, cfg, nm);
         static const int phase_of[6] = {PDDP_PHASE_BP, PDDP_PHASE_FP, PDDP_PHASE_FP, PDDP_PHASE_LS, PDDP_PHASE_NIS, PDDP_PHASE_NIS};
-        const int part_of[6] = {-1, 0, maps_in_rollouts() ? -1 : 1, -1, 0, 1};      // (a rollout kernel that begins with the sweep is timed as it runs in production)
+        const int part_of[6] = {-1, 0, plan.maps_in_rollouts ? -1 : 1, -1, 0, 1};      // (a rollout kernel that begins with the sweep is timed as it runs in production)
         HIPCHK(hipStreamSynchronize(stream));
         note_sweeps_enqueued();
         if (int erc = need_events(7 * (size_t)sweeps)) return erc;
@@ -587,11 +488,11 @@ struct Solver : SolverBase {
     }
     // production sweeps leave the reference-layout views behind (marked here, not only in launch_fp: a hipGraph REPLAY does not pass through the launch functions)
     void note_sweeps_enqueued() {
-        if (sweep_fused || mq_fused) fs_vars_stale = true;
-        if (cf_fp && cf_fp_staged) cand_stale = true;
+        if (plan.sweep_fused || plan.mq_fused) fs_vars_stale = true;
+        if (plan.cf_fp && plan.cf_fp_staged) cand_stale = true;
     }
     int iterate(int sweeps) override {
-        if (bp_mfma && !keep_all_ctg()) lean_ctg_ran = true;
+        if (plan.bp_mfma && !keep_all_ctg()) lean_ctg_ran = true;
         if (sweeps > 0) note_sweeps_enqueued();
         if (cfg.use_graph) {
             if (!graph || graph_mode != bench_mode + 2 * sp.max_iter) {
@@ -622,7 +523,7 @@ struct Solver : SolverBase {
         if (sweeps > 0) note_sweeps_enqueued();
         if (int erc = need_events(6 * (size_t)sweeps)) return erc;
         static const int phase_of[5] = {PDDP_PHASE_BP, PDDP_PHASE_FP, PDDP_PHASE_FP, PDDP_PHASE_LS, PDDP_PHASE_NIS};
-        const bool own_sweep = !maps_in_rollouts();                                  // (otherwise the rollout kernel begins with it: row 4 stays 0)
+        const bool own_sweep = !plan.maps_in_rollouts;                                  // (otherwise the rollout kernel begins with it: row 4 stays 0)
         const int part_of[5] = {-1, 0, own_sweep ? 1 : -1, -1, -1};
         for (int i = 0; i < sweeps; i++) {
             HIPCHK(hipEventRecord(trace_ev[6 * i], stream));
@@ -848,8 +749,7 @@ struct Solver : SolverBase {
         bool split_roll = false;
         const int tsm = (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0;
         if constexpr (P::PLANT == 4 && INTEG == 1 && sizeof(T) == 4) {                // float arm with a built-in robot model: the warm-start rollout split over two waves
-            const char* fpenv = ksel_fp(cfg);
-            if (tl_variant >= 0 && !(fpenv && (std::string(fpenv) == "lg" || std::string(fpenv) == "coop"))) {
+            if (plan.mpc_split_roll) {
                 split_roll = true;
                 if (from) {
                     if (tl_variant == 0) hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T, 0>), dim3(B), dim3(512), 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
@@ -987,13 +887,7 @@ struct Solver : SolverBase {
     const Solver* intake_of = nullptr;             // set on the intake itself: the handle it serves
     int* d_slot_idx = nullptr;                     // [kSlotIntakeMax] the slot indices of the chunk in flight
     unsigned char* d_slot_stage = nullptr; size_t d_slot_stage_cap = 0;      // pddp_store_problems: the packed rows of one chunk
-    void adopt_selection(const Solver& o) {
-        nis_tl7_batch = o.nis_tl7_batch; bp_lane_groups = o.bp_lane_groups; fp_coop = o.fp_coop; fp_split = o.fp_split; fp_two_wave = o.fp_two_wave; ls_many = o.ls_many;
-        fp_path = o.fp_path; tl_variant = o.tl_variant; tl_grav = o.tl_grav;
-        cf_bp = o.cf_bp; cf_fp = o.cf_fp; cf_nis = o.cf_nis; gl_bp32 = o.gl_bp32; gl_nis8 = o.gl_nis8; cl_bp = o.cl_bp; mq_bp = o.mq_bp; mq_fused = o.mq_fused;
-        cf_fp_staged = o.cf_fp_staged; kb_nis = o.kb_nis; gl_bp = o.gl_bp; gl_nis = o.gl_nis; cf_serial = o.cf_serial; bp_wide = o.bp_wide;
-        sweep_fused = o.sweep_fused; sweep_kind = o.sweep_kind; bp_mfma = o.bp_mfma;
-    }
+    void adopt_selection(const Solver& o) { plan = o.plan; tl_variant = o.tl_variant; tl_grav = o.tl_grav; }
     int slot_chunk() const { return cfg.batch < kSlotIntakeMax ? cfg.batch : kSlotIntakeMax; }
     int ensure_slot_idx() {
         if (!d_slot_idx && hipMalloc((void**)&d_slot_idx, kSlotIntakeMax * sizeof(int)) != hipSuccess) return fail(PDDP_ENOMEM, "hipMalloc failed for the slot indices");
@@ -1002,7 +896,7 @@ struct Solver : SolverBase {
     int ensure_intake() {
         // the arrays that exist only on some kernel families must exist on both sides (pddp_set_array("model_*") can move a handle to another family)
         if (intake && ((intake->b.xw != nullptr) != (b.xw != nullptr) || intake->b.xw_rec != b.xw_rec || (intake->b.ABc != nullptr) < (b.ABc != nullptr) ||
-                       (intake->b.Hc != nullptr) < (b.Hc != nullptr) || intake->fp_path != fp_path)) {
+                       (intake->b.Hc != nullptr) < (b.Hc != nullptr) || intake->plan.fp_path != plan.fp_path)) {
             HIPCHK(hipStreamSynchronize(stream));
             delete intake; intake = nullptr;
         }
@@ -1247,7 +1141,7 @@ struct Solver : SolverBase {
         else if (phase == PDDP_PHASE_BP_FUSED || phase == PDDP_PHASE_SWEEP_FUSED) {
             // the production sweep path under teacher forcing: the matrix-core backward pass composes the segment maps (and writes every cost-to-go slot, not
             // A - B K / B du); then k_sweep_maps alone -- the candidates' segment start states land in xs
-            if (!sweep_fused && !mq_fused) return fail(PDDP_EINVAL, "PDDP_PHASE_BP_FUSED / _SWEEP_FUSED: this handle's selection has no fused sweep (matrix-core backward pass -- the KUKA arm's, or the 12-state plants' with the record rollouts --, M > 1, no kernels.sweep override)");
+            if (!plan.sweep_fused && !plan.mq_fused) return fail(PDDP_EINVAL, "PDDP_PHASE_BP_FUSED / _SWEEP_FUSED: this handle's selection has no fused sweep (matrix-core backward pass -- the KUKA arm's, or the 12-state plants' with the record rollouts --, M > 1, no kernels.sweep override)");
             phase_fused_sweep = true;
             if (phase == PDDP_PHASE_BP_FUSED) launch_sweep(stream, PDDP_PHASE_BP, 1);
             else launch_fp(stream, 0, 1, 0);

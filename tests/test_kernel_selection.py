@@ -71,6 +71,14 @@ def test_selection_overrides_reach_the_older_kernels():
     assert kernels(4, 64, dict(bp="lg", fp="lg"), **KUKA)[0] != "k_bp_mfma"
 
 
+def test_finite_differences_report_the_wave_cooperative_setup_they_launch():
+    """USE_FINITE_DIFF: [A B] comes from the plant's `dynamics`, which only the wave-cooperative setup kernel evaluates column by column -- behind lane-group rollouts.
+    The name is the plan's enum the launch switches over (csrc/kernel_plan.hpp), so it is what runs."""
+    kw = dict(KUKA, N=16, M=2, A=4)
+    assert kernels(4, 1, **kw)[-2:] == ["k_fp_tl4", "k_nis_tl7"]
+    assert kernels(4, 1, use_finite_diff=1, **kw)[-3:] == ["k_fp_lg", "k_ls", "k_nis"]
+
+
 @pytest.mark.parametrize("ee", [0, 1])
 def test_large_batches_run_one_thread_per_rollout_and_per_knot(ee):
     kw = dict(KUKA, ee_cost=ee, **(dict(mpc_mode=1, ignore_max_rho_exit=0) if ee else {}))
