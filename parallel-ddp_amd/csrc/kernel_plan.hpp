@@ -1,6 +1,8 @@
 // Which kernel family runs each phase of a handle's sweep: ONE pure function of the configuration, a few compile-time facts of the plant and whether the robot tables are
-// a built-in model's.  The Solver (solver_impl.hpp) holds the result as `plan`, its launch functions read it, its intake area copies it, pddp_time_kernels reports the
-// names resolved here.  State that changes while a handle runs (phase hooks, MPC use, an overridden H, a dropped compact layout) is not plan and stays in the Solver.
+// a built-in model's.  The Solver (solver_impl.hpp) holds the result as `plan`, its intake area copies it, pddp_time_kernels reports the names resolved here, and its
+// launch functions are switches over the plan's kernel enums: launch_bp and launch_nis directly, launch_fp over what plan_fp_launch makes of them for the way the forward
+// pass is asked for (FpMode: production, one kernel alone, the initial rollout, the phase hooks).  State that changes while a handle runs (MPC use, an overridden H, a
+// dropped compact layout, the line search's mode) is not plan and stays in the Solver.
 // Host code only, no HIP header, no environment (tests/native/kernel_plan_host_check.cpp holds it to the recorded selection table without a GPU).
 #pragma once
 #include <cstddef>
@@ -34,7 +36,7 @@ inline CfNisSel sel_cf_nis(const pddp_config& c) { return kernel_sel(c.kernels.c
 // The kernel of every slot of pddp_time_kernels that has one (slot 4, the former winner re-roll, has none); the numbers index kKernelNames.
 enum BpKernel { kBpCoop = 0, kBpWide, kBpLg, kBpMfma, kBpTs, kBpGl, kBpCl, kBpMq };
 enum SweepKernel { kSweepNone = 8, kSweepLg, kSweepSt, kSweepWg, kSweepMaps, kSweepCf, kSweepMapsCf };      // none: the rollout kernel sweeps itself
-enum FpKernel { kFpKernCoop = 15, kFpKernLg, kFpKernTl, kFpKernTl2, kFpKernTl4, kFpKernTs, kFpKernCf };
+enum FpKernel { kFpKernNone = -1, kFpKernCoop = 15, kFpKernLg, kFpKernTl, kFpKernTl2, kFpKernTl4, kFpKernTs, kFpKernCf };        // none: a call for the sweep alone (FpLaunch), never a plan's
 enum LsKernel { kLsNone = 22, kLsWg, kLsMany };                                                              // none: the rollout kernel ends with the line search
 enum NisKernel { kNisCoop = 25, kNisLg, kNisTl, kNisTl7, kNisTs, kNisGl, kNisKb };
 inline const char* kernel_name(int k) {
@@ -130,7 +132,7 @@ struct KernelPlan {
     bool ab_compact = false;       // "ABc": [A B] of the arm in the compact layout
     bool h_compact = false;        // "Hc": the end-effector cost's 7 x 7 position block
     bool fp_coop_lds = false;      // k_fp's dynamic LDS attribute has to cover the handle's segments
-    // what pddp_time_kernels reports and the dispatch of launch_sweep / launch_nis follows
+    // what pddp_time_kernels reports and launch_bp / launch_fp / launch_nis switch over (the forward pass through plan_fp_launch below)
     BpKernel bp = kBpCoop; SweepKernel sweep = kSweepNone; FpKernel fp = kFpKernCoop; LsKernel ls = kLsWg; NisKernel nis = kNisCoop;
 };
 
@@ -243,6 +245,52 @@ inline KernelPlan make_kernel_plan(const pddp_config& c, const PlantTraits& t, b
 // path has no separate kernel for a slot
 inline void plan_kernel_names(const KernelPlan& p, const pddp_config& c, const char* out[6]) {
     out[0] = kernel_name(p.bp); out[1] = kernel_name(c.M > 1 ? p.sweep : kSweepNone); out[2] = kernel_name(p.fp); out[3] = kernel_name(p.ls); out[4] = ""; out[5] = kernel_name(p.nis);
+}
+
+// The ways the forward pass (linear sweep + rollouts) is asked for.
+enum FpMode {
+    kFpProduction,        // a sweep of pddp_iterate / a captured graph; the timing slot of a rollout kernel that sweeps itself
+    kFpSweepOnly,         // the linear sweep's own kernel alone (slot 1 of pddp_time_kernels, row 4 of the traced iteration)
+    kFpRolloutsOnly,      // the rollout kernel alone (slot 2; a kernel that sweeps itself still does)
+    kFpInitial,           // the optional rollout of a load: one candidate, every segment from the loaded state
+    kFpHook,              // pddp_run_phase(PDDP_PHASE_FP): teacher-forced sweep + rollouts, every candidate's x, u, d stored in the reference's arrays
+    kFpHookFusedSweep,    // pddp_run_phase(PDDP_PHASE_SWEEP_FUSED): the production sweep from the composed maps, alone (run_phase refuses a handle without one)
+    kFpHookRollouts       // pddp_run_phase(PDDP_PHASE_ROLLOUT): the hook's rollouts without any sweep, from the start states in xs
+};
+// What one call launches: launch_fp_sweep / launch_fp_rollouts (solver_impl.hpp) switch over `sweep` and `fp` and pass the rest on.
+struct FpLaunch {
+    SweepKernel sweep = kSweepNone;      // none: no sweep launch
+    FpKernel fp = kFpKernNone;           // none: no rollout launch
+    int seed = 0;                        // where the rollouts start: 0 the sweep's states, 1 the loaded trajectory, 2 the start states in xs (k_fp's argument; no_sweep of k_fp_ts)
+    bool store_candidates = false;       // k_fp_tl writes every candidate's x, u, d
+    bool maps_prologue = false;          // k_fp_tl4 begins with the sweep
+    bool ls_tail = false;                // k_fp_tl4 ends with the line search
+    bool cand_to_xw = false;             // k_cand_to_xw follows: the candidate-major arrays into the records
+    bool cand_stale = false;             // the call leaves the candidate-major arrays behind the records
+};
+// In production: plan.sweep (with M > 1) and plan.fp, the kernels pddp_time_kernels names.  Every other mode is that with the deviations stated below.
+inline FpLaunch plan_fp_launch(const KernelPlan& p, const pddp_config& c, FpMode mode) {
+    FpLaunch L;
+    const bool lg = c.plant == 4 && !p.fp_coop, records = p.cf_records;
+    const bool hook = mode == kFpHook || mode == kFpHookFusedSweep || mode == kFpHookRollouts;
+    const SweepKernel prod = c.M > 1 ? p.sweep : kSweepNone;
+    const SweepKernel alone = p.maps_in_rollouts ? kSweepMaps : prod;      // asked for alone, the sweep of a rollout kernel that begins with it is the kernel that prologue replaces
+    if (mode == kFpProduction) L.sweep = prod;
+    if (mode == kFpSweepOnly) L.sweep = alone;
+    if (mode == kFpHookFusedSweep && (alone == kSweepMaps || alone == kSweepMapsCf)) L.sweep = alone;       // the production sweep where that applies composed maps
+    if (mode != kFpSweepOnly && mode != kFpHookFusedSweep) L.fp = p.fp;
+    L.seed = mode == kFpInitial ? 1 : mode == kFpHookRollouts ? 2 : 0;
+    L.store_candidates = hook;
+    L.maps_prologue = p.maps_in_rollouts && mode == kFpProduction;
+    L.ls_tail = p.ls_in_rollouts && (mode == kFpProduction || mode == kFpRolloutsOnly);
+    L.cand_stale = records && !hook && mode != kFpInitial;
+    // the hook's sweep must read the teacher-forced A - B K / B du, so it is sweep_kind's kernel and never the maps (the other families sweep inside their hook rollouts)
+    if (mode == kFpHook && lg && c.M > 1) L.sweep = p.sweep_kind == 2 ? kSweepWg : p.sweep_kind == 1 ? kSweepSt : kSweepLg;
+    // the hook wants the reference's candidate-major arrays: k_fp_ts, then k_cand_to_xw, instead of the record rollouts
+    if (records && (mode == kFpHook || mode == kFpHookRollouts)) { L.fp = kFpKernTs; L.cand_to_xw = true; }
+    // the initial rollout exists on lane groups, or on k_fp: for the arm with USE_LIMITS_FLAG / USE_SMOOTH_ABS, and for every other plant
+    if (mode == kFpInitial) L.fp = (lg && !c.use_limits && !c.use_smooth_abs) ? kFpKernLg : kFpKernCoop;
+    return L;
 }
 
 }  // namespace pddp

@@ -92,7 +92,6 @@ struct Solver : SolverBase {
         drop_graph();
         return 0;
     }
-    bool phase_fused_sweep = false; // pddp_run_phase(PDDP_PHASE_BP_FUSED / _SWEEP_FUSED): the teacher-forcing hook runs the production sweep path (maps composed in the backward pass)
     bool mpc_used = false;         // pddp_mpc_solve ran on this handle: its warm start shifts every cost-to-go slot, so the backward pass keeps writing all of them
     bool lean_ctg_ran = false;     // sweeps ran that left the interior cost-to-go slots unwritten (config.boundary_cost_to_go_only): a warm-started MPC call would shift stale slots
     // every knot's P, p written (the reference's d_P / d_p) unless the caller opted out; MPC handles always keep them (MPCHelpers.cuh:602-655 shifts the whole arrays)
@@ -182,14 +181,11 @@ struct Solver : SolverBase {
         }
         fp_lds = FpLds<P, T>::bytes(c.M, c.N);
         if constexpr (P::PLANT == 4) {                                 // lane-group forward pass: A * (N + M) elements of dynamic LDS per workgroup
-            const size_t a_wg = (c.A > 8 && c.A % 8 == 0) ? 8 : c.A;       // candidates per workgroup (launch_fp)
+            const size_t a_wg = (c.A > 8 && c.A % 8 == 0) ? 8 : c.A;       // candidates per workgroup (launch_fp_rollouts)
             const size_t lds = a_wg * (c.N + c.M) * sizeof(T);
             if (lds > 160 * 1024) return fail(PDDP_EINVAL, "forward-pass LDS footprint (candidates per workgroup * (N + M) elements) exceeds 160 KiB: reduce A or N");
             if (lds > 48 * 1024) {
-                const void* ks[6] = {reinterpret_cast<const void*>(&k_fp_lg<T, 256, false>), reinterpret_cast<const void*>(&k_fp_lg<T, 512, false>),
-                                     reinterpret_cast<const void*>(&k_fp_lg<T, 1024, false>), reinterpret_cast<const void*>(&k_fp_lg<T, 256, true>),
-                                     reinterpret_cast<const void*>(&k_fp_lg<T, 512, true>), reinterpret_cast<const void*>(&k_fp_lg<T, 1024, true>)};
-                for (const void* k : ks) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                for (int k = 0; k < 6; k++) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fp_lg_kernel(k % 3, k >= 3)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             }
         }
         if (plan.fp_coop_lds) {
@@ -231,7 +227,7 @@ struct Solver : SolverBase {
         HIPCHK(hipMemsetAsync(b.tshift, 0, B * sizeof(int), stream));
         if (rollout) {                                               // forwardRolloutFlag (:642-648)
             launch_init_cost(stream, ignore_first_defect, 1, ee, 0);   // state.cur = 0
-            launch_fp(stream, 1);
+            launch_fp(stream, kFpInitial);
             hipLaunchKernelGGL((k_adopt_slot0<P, T>), dim3(N, B), dim3(64), 0, stream, b, dm);
         }
         launch_init_cost_and_setup(stream, ignore_first_defect, rollout, 0);
@@ -252,87 +248,75 @@ struct Solver : SolverBase {
         launch_nis(s, 1);
         if (ee) launch_init_cost(s, ignore_first_defect, rollout, 2, keep_alpha);
     }
-    // forward pass: the arm runs on lane groups (fp_lg.hpp), the closed-form plants on the wave-cooperative kernel
-    // part: -1 everything; 0 only the linear sweep kernel (when the path has a separate one); 1 only the rollout kernel (per-kernel timing; kernels that sweep
-    // themselves still do); 2 the rollouts WITHOUT any sweep, from the start states in xs (PDDP_PHASE_ROLLOUT)
-    bool launch_sweep_maps_cf(hipStream_t s) {                // the record rollouts' sweep from the maps the fused matrix-core backward pass left (false: not this handle's path)
-        if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4) {
-            if (plan.mq_fused) { hipLaunchKernelGGL((k_sweep_maps_cf<P, T>), dim3((cfg.batch + 3) / 4), dim3(64), 0, s, b, dm, (int)cfg.batch); return true; }
-        }
-        return false;
+    // forward pass: plan_fp_launch (kernel_plan.hpp) resolves what `mode` launches -- in production plan.sweep and plan.fp, the kernels pddp_time_kernels names --, the
+    // two switches below launch it.  What is not plan is applied here: the line search's mode, the robot model's variant, the arrays this handle has.
+    void launch_fp(hipStream_t s, FpMode mode) {
+        const FpLaunch L = plan_fp_launch(plan, cfg, mode);
+        if (L.cand_stale) cand_stale = true;
+        launch_fp_sweep(s, L);
+        launch_fp_rollouts(s, L);
     }
-    void launch_fp(hipStream_t s, int init_rollout, int store_candidates = 0, int part = -1) {
+    // the record kernels of the closed-form plants (kernels.hpp fp_cf_body): whole problems per wavefront, the step-size count a template argument
+    template <int AA> void launch_cf(hipStream_t s, bool rollouts) {
+        if constexpr (P::PLANT != 4 && P::kScalarPlugin && (64 / AA) * P::NX <= 64) {
+            const unsigned B = cfg.batch;
+            const dim3 grid((B + 64 / AA - 1) / (64 / AA));
+            if (rollouts) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B); });
+            else hipLaunchKernelGGL((k_sweep_cf<P, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B);
+        }
+    }
+    // k_fp_lg by workgroup size (0: up to 256 threads, 1: 512, 2: 1024) and cost family
+    using FpLgKernel = void (*)(Buffers<T>, Dims, CostWeights<T>, T, int);
+    static FpLgKernel fp_lg_kernel(int size, bool ee) {
+        static constexpr FpLgKernel k[2][3] = {{&k_fp_lg<T, 256, false>, &k_fp_lg<T, 512, false>, &k_fp_lg<T, 1024, false>}, {&k_fp_lg<T, 256, true>, &k_fp_lg<T, 512, true>, &k_fp_lg<T, 1024, true>}};
+        return k[ee][size];
+    }
+    void launch_fp_sweep(hipStream_t s, const FpLaunch& L) {
         const unsigned B = cfg.batch;
-        bool lane_groups = false;
-        if constexpr (P::PLANT == 4) lane_groups = !plan.fp_coop && !(init_rollout && (cfg.use_limits || cfg.use_smooth_abs));       // PDDP_FP=coop: the wave-cooperative forward pass / setup kernels (comparison tests); the initial rollout of a thread-lane handle with USE_LIMITS_FLAG too
-        if (!lane_groups) {
-            bool serial = false, records_ran = false;
-            if constexpr (P::PLANT != 4) {      // (the arm has its own families: no thread-serial instantiation of its cooperative bodies)
-                if (phase_fused_sweep && part == 0) { launch_sweep_maps_cf(s); return; }      // PDDP_PHASE_SWEEP_FUSED: the candidates' segment start states land in their records (xw)
-                const bool records = plan.cf_fp && plan.cf_fp_staged && !init_rollout && part != 2 && !store_candidates;      // (the phase hook wants the reference's candidate-major arrays: k_fp_ts, then k_cand_to_xw)
-                if (records) cand_stale = true;
-                // two launches: the linear sweep (segment start states -> the candidates' records), then the rollouts (kernels.hpp fp_cf_body); part 0 / 1 = only the one / the other
-                if constexpr (P::kScalarPlugin && (64 / 16) * P::NX <= 64) {
-                    if (records && cfg.A == 16) {
-                        if (part != 1 && cfg.M > 1) { if (!launch_sweep_maps_cf(s)) hipLaunchKernelGGL((k_sweep_cf<P, INTEG, T, 16>), dim3((B + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, (int)B); }
-                        if (part != 0) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, 16>), dim3((B + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, (int)B); });
-                        return;
-                    }
-                }
-                if constexpr (P::kScalarPlugin && (64 / 8) * P::NX <= 64) {
-                    if (records && cfg.A == 8) {
-                        if (part != 1 && cfg.M > 1) { if (!launch_sweep_maps_cf(s)) hipLaunchKernelGGL((k_sweep_cf<P, INTEG, T, 8>), dim3((B + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, (int)B); }
-                        if (part != 0) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, 8>), dim3((B + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, (int)B); });
-                        return;
-                    }
-                }
-                if (part == 0) return;                                  // (the paths below sweep inside their rollout kernel)
-                if (!serial && plan.cf_fp && !init_rollout) { with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, part == 2 ? 1 : 0); }); serial = true; }
-            }
-            if (part == 0) return;
-            if (!serial) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(init_rollout ? 1 : cfg.A, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, init_rollout ? 1 : (part == 2 ? 2 : 0)); });
-            if constexpr (P::PLANT != 4) { if (b.xw && !records_ran && !init_rollout) hipLaunchKernelGGL((k_cand_to_xw<P, T>), dim3((unsigned)(((size_t)B * cfg.N * cfg.A + 255) / 256)), dim3(256), 0, s, b, dm, (int)B); }
-            return;
+        switch (L.sweep) {
+        case kSweepNone: break;
+        case kSweepLg:
+            if constexpr (P::PLANT == 4) hipLaunchKernelGGL((k_sweep_lg<T>), dim3((cfg.A + kLgPerWave - 1) / kLgPerWave, B), dim3(64), 0, s, b, dm, dt);
+            break;
+        case kSweepSt: if constexpr (P::PLANT == 4 && sizeof(T) == 4) launch_sweep_st(s, b, dm, (int)B); break;
+        case kSweepWg: if constexpr (P::PLANT == 4 && sizeof(T) == 4) launch_sweep_wg(s, b, dm, (int)B); break;
+        case kSweepMaps: if constexpr (P::PLANT == 4) launch_sweep_maps<T>(s, b, dm, (int)B); break;
+        case kSweepCf: if (cfg.A == 16) launch_cf<16>(s, false); else if (cfg.A == 8) launch_cf<8>(s, false); break;      // segment start states -> the candidates' records
+        case kSweepMapsCf:        // the same from the maps the fused matrix-core backward pass left
+            if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4) hipLaunchKernelGGL((k_sweep_maps_cf<P, T>), dim3((B + 3) / 4), dim3(64), 0, s, b, dm, (int)B);
+            break;
         }
-        if constexpr (P::PLANT == 4) {
-            const int A_all = init_rollout ? 1 : cfg.A;
-            const unsigned chunks = (A_all > 8 && A_all % 8 == 0) ? A_all / 8 : 1;      // one workgroup per 8 candidates when they tile exactly (see k_fp_lg)
-            const int A_eff = A_all / chunks;
-            const unsigned waves = (A_eff * cfg.M + kLgPerWave - 1) / kLgPerWave;
-            if (!init_rollout && cfg.M > 1 && part != 1 && part != 2) {
-                bool st = false;
-                const bool in_rollouts = plan.maps_in_rollouts && part == -1 && !store_candidates;      // (k_fp_tl4 begins with the sweep)
-                if (in_rollouts) st = true;
-                else if (plan.sweep_fused && (!store_candidates || phase_fused_sweep)) { launch_sweep_maps<T>(s, b, dm, (int)B); st = true; }
-                if constexpr (sizeof(T) == 4) {
-                    if (st) {}
-                    else if (plan.sweep_kind == 2) { launch_sweep_wg(s, b, dm, (int)B); st = true; }
-                    else if (plan.sweep_kind == 1) { launch_sweep_st(s, b, dm, (int)B); st = true; }
-                }
-                if (!st) hipLaunchKernelGGL((k_sweep_lg<T>), dim3((cfg.A + kLgPerWave - 1) / kLgPerWave, B), dim3(64), 0, s, b, dm, dt);
+    }
+    void launch_fp_rollouts(hipStream_t s, const FpLaunch& L) {
+        const unsigned B = cfg.batch;
+        const int A_all = L.seed == 1 ? 1 : cfg.A;                  // the initial rollout: one candidate
+        switch (L.fp) {
+        case kFpKernNone: break;
+        case kFpKernTl:           // one thread per (candidate, segment) rollout
+            if constexpr (P::PLANT == 4) launch_fp_tl<T>(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B, L.store_candidates ? 1 : 0);
+            break;
+        case kFpKernTl2: if constexpr (P::PLANT == 4 && sizeof(T) == 4) launch_fp_tl2(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B); break;
+        case kFpKernTl4:
+            if constexpr (P::PLANT == 4) launch_fp_tl4<T>(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B, sp, L.ls_tail ? bench_mode : -1, L.maps_prologue);
+            break;
+        case kFpKernLg:
+            if constexpr (P::PLANT == 4) {
+                const unsigned chunks = (A_all > 8 && A_all % 8 == 0) ? A_all / 8 : 1;      // one workgroup per 8 candidates when they tile exactly (see k_fp_lg)
+                const int A_eff = A_all / chunks;
+                const unsigned waves = (A_eff * cfg.M + kLgPerWave - 1) / kLgPerWave;
+                hipLaunchKernelGGL(fp_lg_kernel(waves <= 4 ? 0 : waves <= 8 ? 1 : 2, cfg.ee_cost != 0), dim3(B, chunks), dim3(64 * waves), (size_t)A_eff * (cfg.N + cfg.M) * sizeof(T), s,
+                                   b, dm, cw, dt, L.seed == 1 ? 1 : 0);
             }
-            if (part == 0) return;
-            if (!init_rollout && plan.fp_split) {
-                bool two = false;
-                if constexpr (sizeof(T) == 4) { if (plan.fp_two_wave) { launch_fp_tl2(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B); two = true; } }
-                if (!two) launch_fp_tl4<T>(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B, sp, (plan.ls_in_rollouts && !store_candidates && part != 2) ? bench_mode : -1,
-                                           plan.maps_in_rollouts && part == -1 && !store_candidates);
-                return;
-            }
-            if (!init_rollout && plan.fp_path == kFpTl) {               // one thread per (candidate, segment) rollout
-                launch_fp_tl<T>(s, tl_variant, b, dm, cw, dt, tl_grav, (int)B, store_candidates);
-                return;
-            }
-            const size_t lds = (size_t)A_eff * (cfg.N + cfg.M) * sizeof(T);
-            const dim3 grid(B, chunks);
-            if (cfg.ee_cost) {
-                if (waves <= 4) hipLaunchKernelGGL((k_fp_lg<T, 256, true>), grid, dim3(64 * waves), lds, s, b, dm, cw, dt, init_rollout);
-                else if (waves <= 8) hipLaunchKernelGGL((k_fp_lg<T, 512, true>), grid, dim3(64 * waves), lds, s, b, dm, cw, dt, init_rollout);
-                else hipLaunchKernelGGL((k_fp_lg<T, 1024, true>), grid, dim3(64 * waves), lds, s, b, dm, cw, dt, init_rollout);
-            } else if (waves <= 4) hipLaunchKernelGGL((k_fp_lg<T, 256>), grid, dim3(64 * waves), lds, s, b, dm, cw, dt, init_rollout);
-            else if (waves <= 8) hipLaunchKernelGGL((k_fp_lg<T, 512>), grid, dim3(64 * waves), lds, s, b, dm, cw, dt, init_rollout);
-            else hipLaunchKernelGGL((k_fp_lg<T, 1024>), grid, dim3(64 * waves), lds, s, b, dm, cw, dt, init_rollout);
+            break;
+        case kFpKernCf: if (cfg.A == 16) launch_cf<16>(s, true); else if (cfg.A == 8) launch_cf<8>(s, true); break;
+        case kFpKernTs:           // (the arm has its own families: no thread-serial instantiation of its cooperative bodies)
+            if constexpr (P::PLANT != 4) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, L.seed == 2 ? 1 : 0); });
+            break;
+        case kFpKernCoop:
+            with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(A_all, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, L.seed); });
+            break;
         }
+        if constexpr (P::PLANT != 4) { if (L.cand_to_xw && b.xw) hipLaunchKernelGGL((k_cand_to_xw<P, T>), dim3((unsigned)(((size_t)B * cfg.N * cfg.A + 255) / 256)), dim3(256), 0, s, b, dm, (int)B); }
     }
     // part: -1 everything; 0 nothing (slot of a former separate winner kernel in the per-kernel timing); 1 only the setup kernel
     // The running knots' cost Hessian the matrix-core backward pass does not read (diag_h) is the one the LAST setup kernel wrote -- the reference's d_H holds exactly
@@ -388,7 +372,8 @@ struct Solver : SolverBase {
             break;
         }
     }
-    void launch_bp(hipStream_t s, int store_candidates) {
+    // fused_hook: pddp_run_phase(PDDP_PHASE_BP_FUSED), the hook's backward pass composing the sweep maps as production's does
+    void launch_bp(hipStream_t s, int store_candidates, bool fused_hook = false) {
         const unsigned B = cfg.batch;
         switch (plan.bp) {
         case kBpMfma:
@@ -398,7 +383,7 @@ struct Solver : SolverBase {
                 const bool ee = cfg.ee_cost != 0;
                 const bool diag_h = !h_overridden && (!ee || b.Hc != nullptr);
                 launch_bp_mfma<T>(s, b, dm, (int)B, diag_h, hw[0], hw[1], hw[2], dt, keep_all_ctg() || store_candidates,
-                                  plan.sweep_fused && (!store_candidates || phase_fused_sweep), ee ? 1 : 0);      // (per-problem weights: the diagonal comes from the table, not from hw)
+                                  plan.sweep_fused && (!store_candidates || fused_hook), ee ? 1 : 0);      // (per-problem weights: the diagonal comes from the table, not from hw)
             }
             break;
         case kBpLg:
@@ -409,7 +394,7 @@ struct Solver : SolverBase {
             break;
         case kBpMq:
             if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4) {
-                const bool fu = plan.mq_fused && (!store_candidates || phase_fused_sweep);      // (the phase hook's backward pass writes A - B K / B du: its sweep is teacher-forced from them)
+                const bool fu = plan.mq_fused && (!store_candidates || fused_hook);      // (the phase hook's backward pass writes A - B K / B du: its sweep is teacher-forced from them)
                 const bool dh = !P::kPluginCost && !h_overridden;   // the plant's own diagonal cost Hessian: not read
                 // (only the instantiations that take the running knots' Hessian from the weights differ with a table of diagonal records: the others read H)
                 if (dh && fu) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
@@ -432,10 +417,11 @@ struct Solver : SolverBase {
         case kBpCoop: hipLaunchKernelGGL((k_bp<P, T>), dim3(cfg.M, B), dim3(64), 0, s, b, dm); break;
         }
     }
+    // one sweep, or its phase `only`.  store_candidates: the phase hook; part 0 / 1: the forward pass's sweep / rollout kernel alone (per-kernel timing)
     void launch_sweep(hipStream_t s, int only = -1, int store_candidates = 0, int part = -1) {
         const unsigned B = cfg.batch;
         if (only < 0 || only == PDDP_PHASE_BP) launch_bp(s, store_candidates);
-        if (only < 0 || only == PDDP_PHASE_FP) launch_fp(s, 0, store_candidates, part);
+        if (only < 0 || only == PDDP_PHASE_FP) launch_fp(s, store_candidates ? kFpHook : part == 0 ? kFpSweepOnly : part == 1 ? kFpRolloutsOnly : kFpProduction);
         if ((only < 0 || only == PDDP_PHASE_LS) && !(plan.ls_in_rollouts && !store_candidates)) {      // (k_fp_tl4 ended with the line search of its problems)
             if (plan.ls_many) hipLaunchKernelGGL((k_ls_many<T>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, b, dm, sp, bench_mode, (int)B);
             else hipLaunchKernelGGL((k_ls<T>), dim3(B), dim3(64), 0, s, b, dm, sp, bench_mode);
@@ -444,7 +430,7 @@ struct Solver : SolverBase {
     }
     // The kernels of one sweep in launch order, by name, and their average duration over `sweeps` sweeps (an event after every launch, one pass).
     // Slots: 0 backward pass, 1 linear sweep, 2 rollouts, 3 line search, 4 winner re-roll, 5 next-iteration setup; a path without a separate kernel
-    // for a slot leaves its name empty and its time 0 (kernel_plan.hpp plan_kernel_names: the names of the enums launch_bp / launch_nis switch over).
+    // for a slot leaves its name empty and its time 0 (kernel_plan.hpp plan_kernel_names: the names of the enums launch_bp / launch_fp / launch_nis switch over).
     int time_kernels(int sweeps, float* ms, char* names, int name_stride) override {
         const char* nm[6];
         plan_kernel_names(plan, cfg, nm);
@@ -1142,13 +1128,11 @@ struct Solver : SolverBase {
             // the production sweep path under teacher forcing: the matrix-core backward pass composes the segment maps (and writes every cost-to-go slot, not
             // A - B K / B du); then k_sweep_maps alone -- the candidates' segment start states land in xs
             if (!plan.sweep_fused && !plan.mq_fused) return fail(PDDP_EINVAL, "PDDP_PHASE_BP_FUSED / _SWEEP_FUSED: this handle's selection has no fused sweep (matrix-core backward pass -- the KUKA arm's, or the 12-state plants' with the record rollouts --, M > 1, no kernels.sweep override)");
-            phase_fused_sweep = true;
-            if (phase == PDDP_PHASE_BP_FUSED) launch_sweep(stream, PDDP_PHASE_BP, 1);
-            else launch_fp(stream, 0, 1, 0);
-            phase_fused_sweep = false;
+            if (phase == PDDP_PHASE_BP_FUSED) launch_bp(stream, 1, true);
+            else launch_fp(stream, kFpHookFusedSweep);
         }
         else if (phase == PDDP_PHASE_ROLLOUT) {
-            launch_fp(stream, 0, 1, 2);
+            launch_fp(stream, kFpHookRollouts);
             hipLaunchKernelGGL((k_reduce_parts<T>), dim3((B + 63) / 64), dim3(64), 0, stream, b, dm, (int)B);
         }
         else if (phase == PDDP_PHASE_BP_COOP) { fs_vars_stale = false; hipLaunchKernelGGL((k_bp<P, T>), dim3(cfg.M, B), dim3(64), 0, stream, b, dm); }

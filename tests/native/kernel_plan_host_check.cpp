@@ -1,9 +1,11 @@
 // Stand-alone host program over the kernel selection (csrc/kernel_plan.hpp).  No GPU, no library.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -I ../../parallel-ddp_amd/csrc kernel_plan_host_check.cpp -o kernel_plan_host_check
-//   ./kernel_plan_host_check            the choices that kernel names do not show, asserted by hand; prints its ok line
+//   ./kernel_plan_host_check            the choices that kernel names do not show, and what every mode of the forward pass launches on eight handles, asserted by hand; prints its ok line
 //   ./kernel_plan_host_check sel        the pddp_config.kernels enums as "field name=value ..." lines (tests/test_kernel_plan.py: include/pddp.h, pyddp.KERNEL_NAMES)
 //   ./kernel_plan_host_check rows       stdin: one configuration per line -- plant dtype N M A integrator batch ee_cost use_limits mpc_mode tl_variant and the nine
 //                                       kernels fields in the order of include/pddp.h; stdout: the names of its sweep's kernels in launch order | xw_rec segmap ABc Hc
+//   ./kernel_plan_host_check fp         stdin: the same rows; stdout: plan_fp_launch of the seven modes in the order of FpMode, " | " between them, each as
+//                                       sweep,rollouts,seed,flags ("-": no launch; flags: store_candidates maps_prologue ls_tail cand_to_xw cand_stale)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -110,6 +112,73 @@ static void check_by_hand() {
     }
 }
 
+// What the forward pass launches, mode by mode (plan_fp_launch), on eight handles: N = 64, M = 4; the arm with Euler steps and a built-in model, cart-pole and quadrotor
+// with RK3.  Read from the launch code of the commit before plan_fp_launch existed, whose nested conditions these records replace.
+struct Want { SweepKernel sweep; FpKernel fp; int seed; bool store, maps, ls, xw, stale; };
+static void check_modes(const pddp_config& c, const Want (&want)[7]) {
+    const KernelPlan p = plan_of(c, 0);
+    for (int m = kFpProduction; m <= kFpHookRollouts; m++) {
+        const FpLaunch L = plan_fp_launch(p, c, (FpMode)m);
+        const Want& w = want[m];
+        if (L.sweep != w.sweep || L.fp != w.fp || L.seed != w.seed || L.store_candidates != w.store || L.maps_prologue != w.maps || L.ls_tail != w.ls || L.cand_to_xw != w.xw || L.cand_stale != w.stale) {
+            std::printf("FAILED: plant %d dtype %d batch %d A %d use_limits %d, mode %d: %s %s seed %d flags %d%d%d%d%d\n", c.plant, c.dtype, c.batch, c.A, c.use_limits, m, kernel_name(L.sweep), kernel_name(L.fp),
+                        L.seed, (int)L.store_candidates, (int)L.maps_prologue, (int)L.ls_tail, (int)L.cand_to_xw, (int)L.cand_stale);
+            std::exit(1);
+        }
+    }
+}
+static void check_fp_modes() {
+    const SweepKernel S0 = kSweepNone; const FpKernel F0 = kFpKernNone;
+    // the order of FpMode: production, sweep only, rollouts only, initial rollout, hook, hook's fused sweep, hook's rollouts from xs
+    // one problem of the float arm: k_fp_tl4 begins with the sweep and ends with the line search -- in production; alone it is neither's place, and the sweep alone is k_sweep_maps
+    const pddp_config arm1 = config_of(4, 0, 64, 4, 8, 1, 1);
+    check_modes(arm1, {{S0, kFpKernTl4, 0, 0, 1, 1, 0, 0}, {kSweepMaps, F0, 0, 0, 0, 0, 0, 0}, {S0, kFpKernTl4, 0, 0, 0, 1, 0, 0}, {S0, kFpKernLg, 1, 0, 0, 0, 0, 0},
+                       {kSweepWg, kFpKernTl4, 0, 1, 0, 0, 0, 0}, {kSweepMaps, F0, 0, 1, 0, 0, 0, 0}, {S0, kFpKernTl4, 2, 1, 0, 0, 0, 0}});
+    const pddp_config arm512 = config_of(4, 0, 64, 4, 8, 1, 512);
+    check_modes(arm512, {{kSweepMaps, kFpKernTl, 0, 0, 0, 0, 0, 0}, {kSweepMaps, F0, 0, 0, 0, 0, 0, 0}, {S0, kFpKernTl, 0, 0, 0, 0, 0, 0}, {S0, kFpKernLg, 1, 0, 0, 0, 0, 0},
+                         {kSweepWg, kFpKernTl, 0, 1, 0, 0, 0, 0}, {kSweepMaps, F0, 0, 1, 0, 0, 0, 0}, {S0, kFpKernTl, 2, 1, 0, 0, 0, 0}});
+    // a double handle has no fused sweep: pddp_run_phase refuses the mode, and there is nothing to launch
+    const pddp_config arm64 = config_of(4, 1, 64, 4, 8, 1, 2);
+    check_modes(arm64, {{kSweepLg, kFpKernLg, 0, 0, 0, 0, 0, 0}, {kSweepLg, F0, 0, 0, 0, 0, 0, 0}, {S0, kFpKernLg, 0, 0, 0, 0, 0, 0}, {S0, kFpKernLg, 1, 0, 0, 0, 0, 0},
+                        {kSweepLg, kFpKernLg, 0, 1, 0, 0, 0, 0}, {S0, F0, 0, 1, 0, 0, 0, 0}, {S0, kFpKernLg, 2, 1, 0, 0, 0, 0}});
+    // USE_LIMITS_FLAG off the thread lanes: k_fp, which sweeps itself, in every mode (its backward pass composes maps, so the hook's fused sweep is accepted and launches nothing)
+    pddp_config armlim = config_of(4, 0, 64, 4, 8, 1, 1); armlim.use_limits = 1;
+    const Want coop[7] = {{S0, kFpKernCoop, 0, 0, 0, 0, 0, 0}, {S0, F0, 0, 0, 0, 0, 0, 0}, {S0, kFpKernCoop, 0, 0, 0, 0, 0, 0}, {S0, kFpKernCoop, 1, 0, 0, 0, 0, 0},
+                          {S0, kFpKernCoop, 0, 1, 0, 0, 0, 0}, {S0, F0, 0, 1, 0, 0, 0, 0}, {S0, kFpKernCoop, 2, 1, 0, 0, 0, 0}};
+    CHECK(plan_of(armlim, 0).sweep_fused);
+    check_modes(armlim, coop);
+    // the record rollouts of the closed-form plants leave the candidate-major arrays behind; the hook fills those (k_fp_ts) and converts
+    const pddp_config cart8 = config_of(2, 0, 64, 4, 8, 3, 4096);
+    check_modes(cart8, {{kSweepCf, kFpKernCf, 0, 0, 0, 0, 0, 1}, {kSweepCf, F0, 0, 0, 0, 0, 0, 1}, {S0, kFpKernCf, 0, 0, 0, 0, 0, 1}, {S0, kFpKernCoop, 1, 0, 0, 0, 0, 0},
+                        {S0, kFpKernTs, 0, 1, 0, 0, 1, 0}, {S0, F0, 0, 1, 0, 0, 0, 0}, {S0, kFpKernTs, 2, 1, 0, 0, 1, 0}});
+    const pddp_config cart4 = config_of(2, 0, 64, 4, 4, 3, 4096);      // four step sizes: no records
+    check_modes(cart4, {{S0, kFpKernTs, 0, 0, 0, 0, 0, 0}, {S0, F0, 0, 0, 0, 0, 0, 0}, {S0, kFpKernTs, 0, 0, 0, 0, 0, 0}, {S0, kFpKernCoop, 1, 0, 0, 0, 0, 0},
+                        {S0, kFpKernTs, 0, 1, 0, 0, 0, 0}, {S0, F0, 0, 1, 0, 0, 0, 0}, {S0, kFpKernTs, 2, 1, 0, 0, 0, 0}});
+    check_modes(config_of(2, 0, 64, 4, 8, 3, 2), coop);
+    const pddp_config quad16 = config_of(3, 0, 64, 4, 16, 3, 2048);    // the matrix-core backward pass composes the maps: k_sweep_maps_cf (reported as k_sweep_maps)
+    check_modes(quad16, {{kSweepMapsCf, kFpKernCf, 0, 0, 0, 0, 0, 1}, {kSweepMapsCf, F0, 0, 0, 0, 0, 0, 1}, {S0, kFpKernCf, 0, 0, 0, 0, 0, 1}, {S0, kFpKernCoop, 1, 0, 0, 0, 0, 0},
+                         {S0, kFpKernTs, 0, 1, 0, 0, 1, 0}, {kSweepMapsCf, F0, 0, 1, 0, 0, 0, 0}, {S0, kFpKernTs, 2, 1, 0, 0, 1, 0}});
+    // production has none of the other modes' deviations: it is plan.sweep + plan.fp ...
+    for (const pddp_config& c : {arm1, arm512, arm64, armlim, cart8, cart4, quad16}) {
+        const KernelPlan p = plan_of(c, 0);
+        const FpLaunch L = plan_fp_launch(p, c, kFpProduction);
+        CHECK(L.sweep == p.sweep && L.fp == p.fp && L.seed == 0 && !L.store_candidates && !L.cand_to_xw);
+    }
+    // ... the record rollouts, not the hook's k_fp_ts + k_cand_to_xw
+    CHECK(plan_fp_launch(plan_of(cart8), cart8, kFpProduction).fp == kFpKernCf && plan_fp_launch(plan_of(cart8), cart8, kFpHook).fp == kFpKernTs);
+    // ... the composed maps, not the hook's sweep over the teacher-forced A - B K
+    CHECK(plan_fp_launch(plan_of(arm512, 0), arm512, kFpProduction).sweep == kSweepMaps && plan_fp_launch(plan_of(arm512, 0), arm512, kFpHook).sweep == kSweepWg);
+    // ... the handle's own rollout kernel, not the initial rollout's lane groups / k_fp
+    CHECK(plan_fp_launch(plan_of(arm512, 0), arm512, kFpProduction).fp == kFpKernTl && plan_fp_launch(plan_of(cart8), cart8, kFpProduction).fp != kFpKernCoop);
+    pddp_config tl_lim = arm512; tl_lim.use_limits = 1;                 // (a thread-lane handle with USE_LIMITS_FLAG: only its initial rollout is k_fp's)
+    CHECK(plan_fp_launch(plan_of(tl_lim, 0), tl_lim, kFpProduction).fp == kFpKernTl && plan_fp_launch(plan_of(tl_lim, 0), tl_lim, kFpInitial).fp == kFpKernCoop);
+    // one segment: no sweep in any mode
+    pddp_config m1 = config_of(4, 0, 64, 1, 8, 1, 512);
+    for (int m = kFpProduction; m <= kFpHookRollouts; m++) CHECK(plan_fp_launch(plan_of(m1, 0), m1, (FpMode)m).sweep == kSweepNone);
+    m1 = config_of(2, 0, 64, 1, 8, 3, 4096);
+    for (int m = kFpProduction; m <= kFpHookRollouts; m++) CHECK(plan_fp_launch(plan_of(m1), m1, (FpMode)m).sweep == kSweepNone);
+}
+
 static void print_sel() {
     std::printf("bp mx=%d lg=%d coop=%d wide=%d\n", kBpSelMx, kBpSelLg, kBpSelCoop, kBpSelWide);
     std::printf("fp tl=%d lg=%d coop=%d tl2=%d tl4=%d\n", kFpSelTl, kFpSelLg, kFpSelCoop, kFpSelTl2, kFpSelTl4);
@@ -122,7 +191,7 @@ static void print_sel() {
     std::printf("cf_nis ts=%d coop=%d gl=%d gl8=%d kb16=%d kb32=%d kb64=%d kb20=%d\n", kCfNisSelTs, kCfNisSelCoop, kCfNisSelGl, kCfNisSelGl8, kCfNisSelKb16, kCfNisSelKb32, kCfNisSelKb64, kCfNisSelKb20);
 }
 
-static int print_rows() {
+static int print_rows(bool modes) {
     int v[20];
     for (;;) {
         int got = 0;
@@ -134,6 +203,15 @@ static int print_rows() {
         c.kernels.bp = v[11]; c.kernels.fp = v[12]; c.kernels.sweep = v[13]; c.kernels.ls = v[14]; c.kernels.ab = v[15];
         c.kernels.cf = v[16]; c.kernels.cf_bp = v[17]; c.kernels.cf_fp = v[18]; c.kernels.cf_nis = v[19];
         const KernelPlan p = plan_of(c, v[10]);
+        if (modes) {
+            for (int m = kFpProduction; m <= kFpHookRollouts; m++) {
+                const FpLaunch L = plan_fp_launch(p, c, (FpMode)m);
+                std::printf("%s%s,%s,%d,%d%d%d%d%d", m ? " | " : "", L.sweep == kSweepNone ? "-" : kernel_name(L.sweep), L.fp == kFpKernNone ? "-" : kernel_name(L.fp), L.seed,
+                            (int)L.store_candidates, (int)L.maps_prologue, (int)L.ls_tail, (int)L.cand_to_xw, (int)L.cand_stale);
+            }
+            std::printf("\n");
+            continue;
+        }
         const char* nm[6];
         plan_kernel_names(p, c, nm);
         for (int k = 0; k < 6; k++) if (nm[k][0]) std::printf("%s ", nm[k]);
@@ -143,8 +221,10 @@ static int print_rows() {
 
 int main(int argc, char** argv) {
     if (argc > 1 && std::strcmp(argv[1], "sel") == 0) { print_sel(); return 0; }
-    if (argc > 1 && std::strcmp(argv[1], "rows") == 0) return print_rows();
+    if (argc > 1 && std::strcmp(argv[1], "rows") == 0) return print_rows(false);
+    if (argc > 1 && std::strcmp(argv[1], "fp") == 0) return print_rows(true);
     check_by_hand();
+    check_fp_modes();
     std::printf("kernel_plan_host_check: ok\n");
     return 0;
 }

@@ -3,7 +3,8 @@
 tests/golden/kernel_selection_table.json is what handles of the library REPORTED (pddp_time_kernels) and ALLOCATED (xw, segmap, ABc, Hc) over a grid of configurations
 that straddles every crossover and every pddp_config.kernels value, recorded once by tools/kernel_plan_table.py on a GPU.  tests/native/kernel_plan_host_check.cpp
 (its own main, -fsanitize=address,undefined) feeds every row's configuration through make_kernel_plan + plan_kernel_names and has to print the same; by hand it asserts
-the choices that names do not show.  The launches follow the same enums (solver_impl.hpp launch_bp / launch_nis), tests/test_kernel_selection.py holds that on the GPU."""
+the choices that names do not show, and what plan_fp_launch makes of the plan in each of the seven ways the forward pass is asked for.  The launches follow the same enums
+(solver_impl.hpp launch_bp / launch_fp / launch_nis), tests/test_kernel_selection.py holds that on the GPU."""
 import json
 import os
 import re
@@ -55,19 +56,50 @@ def test_enum_values_are_the_numbers_of_the_header_and_of_the_binding(host_check
             assert re.search(rf"\b{v} {name}\b", comment), (field, name, v)
 
 
-def test_every_recorded_row_resolves_to_the_recorded_kernels_and_arrays(host_check):
+def _recorded_rows_through(host_check, command):
     table = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_selection_table.json")))
     assert table["fields"][:len(FIELDS)] == FIELDS and table["fields"][len(FIELDS)] == "kernels:" + ",".join(KFIELDS)
     rows = table["rows"]
     assert len(rows) >= 1000
     text = "".join(" ".join(str(v) for v in r[:len(FIELDS)] + r[len(FIELDS)]) + "\n" for r in rows)
-    out = subprocess.run([host_check, "rows"], input=text, capture_output=True, text=True)
+    out = subprocess.run([host_check, command], input=text, capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr
     lines = out.stdout.splitlines()
     assert len(lines) == len(rows)
+    return rows, lines
+
+
+def test_every_recorded_row_resolves_to_the_recorded_kernels_and_arrays(host_check):
+    rows, lines = _recorded_rows_through(host_check, "rows")
     wrong = []
     for r, line in zip(rows, lines):
         names, arrays = line.split("|")
         if names.split() != r[len(FIELDS) + 1] or [int(v) for v in arrays.split()] != r[len(FIELDS) + 2]:
+            wrong.append((r, line))
+    assert not wrong, f"{len(wrong)} of {len(rows)} rows differ, the first: {wrong[:5]}"
+
+
+def test_every_mode_of_the_forward_pass_resolves_on_every_recorded_row(host_check):
+    """plan_fp_launch over the recorded rows, all seven modes (under the sanitizers): production launches the recorded names of slots 1 and 2 -- what GPU handles
+    reported before the launch followed the plan's enums --, a sweep-only mode no rollout kernel, a mode without a sweep launch none."""
+    rows, lines = _recorded_rows_through(host_check, "fp")
+    modes = ["production", "sweep only", "rollouts only", "initial rollout", "hook", "hook, fused sweep", "hook, rollouts"]
+    wrong = []
+    for r, line in zip(rows, lines):
+        got = {}
+        for mode, rec in zip(modes, line.split(" | ")):
+            sweep, fp, seed, flags = rec.split(",")
+            got[mode] = dict(sweep=sweep, fp=fp, seed=int(seed), **dict(zip(("store", "maps", "ls", "xw", "stale"), (int(f) for f in flags))))
+        assert len(got) == 7, line
+        names = r[len(FIELDS) + 1]
+        recorded = ["".join(n for n in names if n.startswith(prefix)) or "-" for prefix in ("k_sweep", "k_fp")]
+        ok = [got["production"]["sweep"], got["production"]["fp"]] == recorded
+        ok = ok and got["sweep only"]["fp"] == got["hook, fused sweep"]["fp"] == "-"
+        ok = ok and all(got[m]["sweep"] == "-" for m in ("rollouts only", "initial rollout", "hook, rollouts"))
+        ok = ok and all(got[m]["fp"].startswith("k_fp") for m in modes if m not in ("sweep only", "hook, fused sweep"))
+        ok = ok and [got[m]["seed"] for m in modes] == [0, 0, 0, 1, 0, 0, 2] and [got[m]["store"] for m in modes] == [0, 0, 0, 0, 1, 1, 1]
+        M = r[FIELDS.index("M")]
+        ok = ok and (M > 1 or all(got[m]["sweep"] == "-" for m in modes))
+        if not ok:
             wrong.append((r, line))
     assert not wrong, f"{len(wrong)} of {len(rows)} rows differ, the first: {wrong[:5]}"
