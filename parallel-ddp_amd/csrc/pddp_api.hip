@@ -189,12 +189,11 @@ extern "C" int pddp_plant_eval(pddp_handle h, int what, int count, const void* x
 extern "C" int pddp_hbm_calibration(int device, size_t bytes, int reps) {
     if (bytes < 4096 || reps < 1) return fail(PDDP_EINVAL, "hbm_calibration: bad arguments");
     HIPCHK(hipSetDevice(device));
-    float *a = nullptr, *b2 = nullptr;
-    HIPCHK(hipMalloc((void**)&a, bytes)); HIPCHK(hipMalloc((void**)&b2, bytes));
-    HIPCHK(hipMemset(a, 1, bytes)); HIPCHK(hipMemset(b2, 0, bytes));
-    for (int i = 0; i < reps; i++) hipLaunchKernelGGL(k_hbm_calib_dword, dim3(256 * 16), dim3(256), 0, 0, a, b2, bytes / sizeof(float));
+    DeviceBuf a, b2;                 // (released on every return)
+    if (!a.reserve(bytes) || !b2.reserve(bytes)) return fail(PDDP_ENODEVICE, "hbm_calibration: hipMalloc failed");
+    HIPCHK(hipMemset(a.ptr, 1, bytes)); HIPCHK(hipMemset(b2.ptr, 0, bytes));
+    for (int i = 0; i < reps; i++) hipLaunchKernelGGL(k_hbm_calib_dword, dim3(256 * 16), dim3(256), 0, 0, a.as<float>(), b2.as<float>(), bytes / sizeof(float));
     HIPCHK(hipGetLastError()); HIPCHK(hipDeviceSynchronize());
-    hipFree(a); hipFree(b2);
     return 0;
 }
 

@@ -81,6 +81,18 @@ inline std::string slots_complaint(int count, const int* idx, int batch) {
     return "";
 }
 
+// f(first, len) for every maximal run of positions [first, first + len) of idx[0 .. count) whose slots ascend by one, in order: what names such a run moves rows of
+// a per-slot table with one transfer (the cost-weight tables, solver_impl.hpp)
+template <typename F>
+inline void for_each_slot_run(int count, const int* idx, F&& f) {
+    for (int i = 0; i < count;) {
+        int j = i + 1;
+        while (j < count && idx[j] == idx[j - 1] + 1) j++;
+        f(i, j - i);
+        i = j;
+    }
+}
+
 #ifdef __HIPCC__
 // `bytes` bytes from src to dst (src null: zeros) by one workgroup, `vec` bytes per lane and access
 __device__ inline void slot_move(unsigned char* dst, const unsigned char* src, unsigned bytes, int vec) {

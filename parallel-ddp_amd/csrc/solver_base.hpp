@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/pddp.h"
+#include "device_mem.hpp"
 
 #if defined(PDDP_USER_PLANT_HEADER) || defined(PDDP_REF_PLANT_FILE)
 #define PDDP_HAS_USER_PLANT 1      /* a `make user` build: plant 5 exists (policy header or reference-form plug-in) */
@@ -25,6 +26,19 @@ static inline int fail(int code, const std::string& msg) { return pddp_internal_
         hipError_t e_ = (call);                                                                              \
         if (e_ != hipSuccess) return fail(PDDP_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
+// the two kinds of memory a handle owns (device_mem.hpp); kFailCode: the error code of a failed allocation of that kind
+struct DeviceMem {
+    static constexpr int kFailCode = PDDP_ENOMEM;
+    static bool alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
+    static void release(void* p) { hipFree(p); }
+};
+struct PinnedMem {
+    static constexpr int kFailCode = PDDP_ENODEVICE;
+    static bool alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess; }
+    static void release(void* p) { hipHostFree(p); }
+};
+using DeviceBuf = pddp::MemBuf<DeviceMem>;
+using PinnedBuf = pddp::MemBuf<PinnedMem>;
 static double now_ms() { timeval t; gettimeofday(&t, nullptr); return t.tv_sec * 1e3 + t.tv_usec * 1e-3; }
 
 struct SolverBase {

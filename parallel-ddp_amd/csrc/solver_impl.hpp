@@ -20,14 +20,22 @@ struct Solver : SolverBase {
     MpcBuffers<T> mb{};
     T* d_xActual = nullptr; T* d_goal_in = nullptr; int* d_shift = nullptr;
     unsigned char* d_mpc_out = nullptr;      // MPC outputs of a control cycle packed per problem by k_mpc_store (one transfer)
-    unsigned char* h_state = nullptr;                              // pinned copy target of the solver states (status polls)
-    unsigned char* h_stage = nullptr; size_t h_stage_bytes = 0;     // pinned host staging of the MPC call (inputs, then outputs): its transfers are asynchronous, one sync per control cycle
+    PinnedBuf h_state;                       // pinned copy target of the solver states (status polls)
+    PinnedBuf h_stage;                       // pinned host staging of the MPC call (inputs, then outputs): its transfers are asynchronous, one sync per control cycle
     Dims dm{};
     SolverParams sp{};
     CostWeights<T> cw{};
     T dt{};
     std::map<std::string, std::pair<void*, size_t>> arrays;
-    std::vector<void*> allocs;
+    std::vector<DeviceBuf> allocs;           // the blocks behind `arrays`, the robot model and mpc_out
+    // A handle's device and pinned memory are MemBufs (device_mem.hpp): members, or elements of `allocs`.  This is the one place that grows one: the stream is waited for
+    // before a block that may still be in use is released, and a failed allocation returns the error code of its kind of memory (PDDP_ENOMEM device, PDDP_ENODEVICE pinned) with the message `what`.
+    // (The wait costs the MPC call's h_stage nothing: its size is a function of cap_batch, N and max_iter, which are fixed per handle, so it never regrows.)
+    template <typename Mem> int reserve(MemBuf<Mem>& buf, size_t bytes, const char* what, size_t min_cap = 0) {
+        if (buf.holds(bytes)) return 0;
+        if (buf.ptr) HIPCHK(hipStreamSynchronize(stream));
+        return buf.reserve(bytes, min_cap) ? 0 : fail(Mem::kFailCode, what);
+    }
     KernelPlan plan;               // which kernel family runs each phase and which optional arrays they need (kernel_plan.hpp); an intake area holds its handle's
     void resolve_plan() { plan = make_kernel_plan(cfg, PlantTraits{P::PLANT, NX, NU, P::kScalarPlugin, P::kPluginCost}, sizeof(T) == 4, tl_variant); }
     int tl_variant = -1;           // which built-in robot model the handle's tables equal (the thread-lane kernels fold it into literals); -1: neither
@@ -100,21 +108,12 @@ struct Solver : SolverBase {
     int graph_mode = -1;
     size_t fp_lds = 0;
 
+    // what is not memory.  The member buffers are released after this body, when the stream is gone: releasing device or pinned memory needs no stream.
     ~Solver() override {
-        if (graph) hipGraphExecDestroy(graph);
-        if (graph_n) hipGraphExecDestroy(graph_n);
+        drop_graph();
         for (hipEvent_t e : trace_ev) hipEventDestroy(e);
-        for (void* p : allocs) hipFree(p);
-        for (void* p : scratch_buf) if (p) hipFree(p);
-        if (d_simb) hipFree(d_simb);
-        if (d_simb_plan) hipFree(d_simb_plan);
-        if (h_simb) hipHostFree(h_simb);
-        if (h_stage) hipHostFree(h_stage);
-        if (h_state) hipHostFree(h_state);
-        delete intake;
         for (hipEvent_t e : slots_ev) if (e) hipEventDestroy(e);
-        if (d_slot_idx) hipFree(d_slot_idx);
-        if (d_slot_stage) hipFree(d_slot_stage);
+        delete intake;                                              // (before the stream it runs on)
         if (stream && !intake_of) hipStreamDestroy(stream);        // (an intake area runs on its handle's stream)
     }
     void register_model(void* dmodel, const ArmModel<T>&) {
@@ -123,10 +122,11 @@ struct Solver : SolverBase {
     }
     void register_model(void*, const EmptyModel&) {}
     template <typename U> int alloc(const char* name, U** out, size_t count) {
-        void* p = nullptr;
-        if (hipMalloc(&p, count * sizeof(U)) != hipSuccess) return fail(PDDP_ENOMEM, std::string("hipMalloc failed for ") + name);
-        if (hipMemset(p, 0, count * sizeof(U)) != hipSuccess) return fail(PDDP_ENODEVICE, "hipMemset failed");
-        allocs.push_back(p); arrays[name] = {p, count * sizeof(U)}; *out = (U*)p;
+        DeviceBuf blk;
+        if (!blk.reserve(count * sizeof(U))) return fail(PDDP_ENOMEM, std::string("hipMalloc failed for ") + name);
+        if (hipMemset(blk.ptr, 0, count * sizeof(U)) != hipSuccess) return fail(PDDP_ENODEVICE, "hipMemset failed");
+        arrays[name] = {blk.ptr, count * sizeof(U)}; *out = blk.template as<U>();
+        allocs.push_back(std::move(blk));
         return 0;
     }
     int init() override {
@@ -159,8 +159,9 @@ struct Solver : SolverBase {
         alpha_table(c, al.data());
         HIPCHK(hipMemcpy(b.alpha, al.data(), A * sizeof(T), hipMemcpyHostToDevice));
         typename P::Model hm; fill_model(hm, c);
-        void* dmodel = nullptr;
-        HIPCHK(hipMalloc(&dmodel, sizeof(hm))); allocs.push_back(dmodel);
+        allocs.emplace_back();
+        if (!allocs.back().reserve(sizeof(hm))) return fail(PDDP_ENODEVICE, "hipMalloc failed for the robot model");
+        void* dmodel = allocs.back().ptr;
         HIPCHK(hipMemcpy(dmodel, &hm, sizeof(hm), hipMemcpyHostToDevice));
         b.model = dmodel;
         register_model(dmodel, hm);
@@ -534,7 +535,7 @@ struct Solver : SolverBase {
         HIPCHK(hipStreamSynchronize(stream));
         cfg.Q1 = Q1; cfg.Q2 = Q2; cfg.R = R; cfg.QF1 = QF1; cfg.QF2 = QF2;
         cw = cost_weights_of<T, P::PLANT>(cfg);
-        if (graph) { hipGraphExecDestroy(graph); graph = nullptr; graph_mode = -1; }   // the weights are kernel arguments baked into the captured sweep
+        drop_graph();                                                // the weights are kernel arguments baked into the captured sweep
         return fill_cost_table();
     }
     int set_cost_ee(const double* v) override {
@@ -549,60 +550,59 @@ struct Solver : SolverBase {
     // The table exists from the first pddp_set_cost_problems on; until then b.cwt is null and every kernel takes the handle-wide record from its arguments, as it always did.
     // Its creation changes which kernels a sweep launches (the matrix-core backward pass and the thread-lane kernels have instantiations of their own) and a kernel
     // argument, so the captured graph goes ONCE; afterwards the graph holds the pointer and a call only writes rows, on the stream, behind what is enqueued there.
-    T* d_cwt = nullptr;
+    DeviceBuf d_cwt;
+    T* cwt_rows() const { return d_cwt.template as<T>(); }
     std::vector<T> cwt_stage;                      // host rows of the call in flight (the call waits for the stream before it returns)
     int cost_record_size() const override { return P::PLANT == 4 && !P::kPluginCost ? cost_record_len(cfg.ee_cost) : 0; }
-    // every row <- the handle-wide record (a table that exists: pddp_set_cost / pddp_set_cost_ee after per-problem weights; the last call wins)
-    int fill_cost_table() {
-        if (!d_cwt || kDiagCost) return 0;                          // (plants 1-3: the table holds diagonal records, which pddp_set_cost has no part in -- the call is as inert there as it always was)
-        const int rec = cost_record_len(cfg.ee_cost);
-        cwt_stage.resize((size_t)cfg.batch * rec);
-        for (int i = 0; i < cfg.batch; i++) cost_record_of<T>(cw, cwt_stage.data() + (size_t)i * rec);
-        HIPCHK(hipMemcpyAsync(d_cwt, cwt_stage.data(), cwt_stage.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+    // The three ways rows of `rec` numbers travel between cwt_stage and the table; each waits for the stream before it returns.
+    // rows i of cwt_stage -> rows idx[i] of the table (to_device) or the reverse: contiguous runs of slots in one transfer each; rows that are not named keep their values
+    int cwt_move_rows(int count, const int* idx, int rec, bool to_device) {
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int len) {
+            T* h = cwt_stage.data() + (size_t)first * rec; T* d = cwt_rows() + (size_t)idx[first] * rec;
+            if (e == hipSuccess) e = to_device ? hipMemcpyAsync(d, h, (size_t)len * rec * sizeof(T), hipMemcpyHostToDevice, stream) : hipMemcpyAsync(h, d, (size_t)len * rec * sizeof(T), hipMemcpyDeviceToHost, stream);
+        });
+        if (e != hipSuccess) return fail(PDDP_ENODEVICE, std::string("cost table: transfer of rows failed: ") + hipGetErrorString(e));
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
+    }
+    int cwt_upload_rows(int count, const int* idx, int rec) { return cwt_move_rows(count, idx, rec, true); }
+    int cwt_download_rows(int count, const int* idx, int rec) { return cwt_move_rows(count, idx, rec, false); }
+    // every one of the table's `rows` rows <- `record` (not a part of cwt_stage)
+    int cwt_fill_rows(int rows, int rec, const T* record) {
+        cwt_stage.resize((size_t)rows * rec);
+        for (int i = 0; i < rows; i++) std::memcpy(cwt_stage.data() + (size_t)i * rec, record, rec * sizeof(T));
+        HIPCHK(hipMemcpyAsync(cwt_rows(), cwt_stage.data(), cwt_stage.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    // every row <- the handle-wide record (a table that exists: pddp_set_cost / pddp_set_cost_ee after per-problem weights; the last call wins)
+    int fill_cost_table() {
+        if (!d_cwt.ptr || kDiagCost) return 0;                      // (plants 1-3: the table holds diagonal records, which pddp_set_cost has no part in -- the call is as inert there as it always was)
+        T row[kCostRecEe];                                          // (the longer of the two records)
+        cost_record_of<T>(cw, row);
+        return cwt_fill_rows(cfg.batch, cost_record_len(cfg.ee_cost), row);
     }
     // numbers per row of the table: the arm's record of its cost family, or the diagonal record of the pendulum, cart-pole and quadrotor
     int table_record_len() const { return kDiagCost ? kDiagRec : cost_record_len(cfg.ee_cost); }
-    int ensure_cost_table(int rows) {
-        if (d_cwt) return 0;
-        void* p = nullptr;
-        if (hipMalloc(&p, (size_t)rows * table_record_len() * sizeof(T)) != hipSuccess) return fail(PDDP_ENOMEM, "hipMalloc failed for the per-problem cost weights");
-        allocs.push_back(p); d_cwt = (T*)p;
-        return 0;
-    }
+    int ensure_cost_table(int rows) { return reserve(d_cwt, (size_t)rows * table_record_len() * sizeof(T), "hipMalloc failed for the per-problem cost weights"); }
     int set_cost_problems(int count, const int* idx, const double* w) override {
         const int rec = cost_record_len(cfg.ee_cost);
-        if (!d_cwt) {
+        if (!d_cwt.ptr) {
             if (int rc = ensure_cost_table(cfg.batch)) return rc;
             if (int rc = fill_cost_table()) return rc;                 // (waits for the stream: nothing in flight reads the old argument set)
-            b.cwt = d_cwt;
+            b.cwt = cwt_rows();
             drop_graph();
         }
-        // contiguous runs of slots go up in one transfer each; rows that are not named keep their values
         cwt_stage.resize((size_t)count * rec);
         cost_records_pack<T>(count, rec, w, cwt_stage.data());
-        for (int i = 0; i < count;) {
-            int j = i + 1;
-            while (j < count && idx[j] == idx[j - 1] + 1) j++;
-            HIPCHK(hipMemcpyAsync(d_cwt + (size_t)idx[i] * rec, cwt_stage.data() + (size_t)i * rec, (size_t)(j - i) * rec * sizeof(T), hipMemcpyHostToDevice, stream));
-            i = j;
-        }
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
+        return cwt_upload_rows(count, idx, rec);
     }
     int get_cost_problems(int count, const int* idx, double* w) override {
         const int rec = cost_record_len(cfg.ee_cost);
         cwt_stage.resize((size_t)count * rec);
-        if (d_cwt) {                                                   // contiguous runs of slots come down in one transfer each, as the setter sends them up
-            for (int i = 0; i < count;) {
-                int j = i + 1;
-                while (j < count && idx[j] == idx[j - 1] + 1) j++;
-                HIPCHK(hipMemcpyAsync(cwt_stage.data() + (size_t)i * rec, d_cwt + (size_t)idx[i] * rec, (size_t)(j - i) * rec * sizeof(T), hipMemcpyDeviceToHost, stream));
-                i = j;
-            }
-            HIPCHK(hipStreamSynchronize(stream));
-        } else for (int i = 0; i < count; i++) cost_record_of<T>(cw, cwt_stage.data() + (size_t)i * rec);
+        if (d_cwt.ptr) { if (int rc = cwt_download_rows(count, idx, rec)) return rc; }
+        else for (int i = 0; i < count; i++) cost_record_of<T>(cw, cwt_stage.data() + (size_t)i * rec);
         for (size_t e = 0; e < (size_t)count * rec; e++) w[e] = (double)cwt_stage[e];
         return 0;
     }
@@ -625,12 +625,9 @@ struct Solver : SolverBase {
             T row[kDiagRec];
             if (!diag_record_builtin<P, T>(cfg.N, row)) return fail(PDDP_EINVAL, "diagonal cost records: the plant's QR(NX + j, N) differs from its Rw(N), so its control weight is not one number");
             if (int rc = ensure_cost_table(cfg.batch)) return rc;
-            cwt_stage.resize((size_t)cfg.batch * kDiagRec);
-            for (int i = 0; i < cfg.batch; i++) std::memcpy(cwt_stage.data() + (size_t)i * kDiagRec, row, sizeof(row));
-            HIPCHK(hipMemcpyAsync(d_cwt, cwt_stage.data(), cwt_stage.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));                   // (nothing in flight reads the old argument set)
+            if (int rc = cwt_fill_rows(cfg.batch, kDiagRec, row)) return rc;      // (waits for the stream: nothing in flight reads the old argument set)
             if (fp_lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fp<DiagTab<P, T>, INTEG, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp_lds));
-            b.cwt = d_cwt;
+            b.cwt = cwt_rows();
             drop_graph();
         }
         return 0;
@@ -642,14 +639,7 @@ struct Solver : SolverBase {
         if (int rc = ensure_diag_table()) return rc;
         cwt_stage.resize((size_t)count * kDiagRec);
         cost_records_pack<T>(count, kDiagRec, w, cwt_stage.data());
-        for (int i = 0; i < count;) {                               // contiguous runs of slots go up in one transfer each; rows that are not named keep their values
-            int j = i + 1;
-            while (j < count && idx[j] == idx[j - 1] + 1) j++;
-            HIPCHK(hipMemcpyAsync(d_cwt + (size_t)idx[i] * kDiagRec, cwt_stage.data() + (size_t)i * kDiagRec, (size_t)(j - i) * kDiagRec * sizeof(T), hipMemcpyHostToDevice, stream));
-            i = j;
-        }
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
+        return cwt_upload_rows(count, idx, kDiagRec);
     }
     int set_diag_cost(const double* w) override {
         if (!kDiagCost) return diag_refuse("pddp_set_diag_cost");
@@ -657,27 +647,17 @@ struct Solver : SolverBase {
         const std::string complaint = diag_records_complaint<T>(1, &zero, w, cfg.batch, NX, NU);
         if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_diag_cost: " + complaint);
         if (int rc = ensure_diag_table()) return rc;
-        cwt_stage.resize((size_t)cfg.batch * kDiagRec);
-        cost_records_pack<T>(1, kDiagRec, w, cwt_stage.data());
-        for (int i = 1; i < cfg.batch; i++) std::memcpy(cwt_stage.data() + (size_t)i * kDiagRec, cwt_stage.data(), kDiagRec * sizeof(T));
-        HIPCHK(hipMemcpyAsync(d_cwt, cwt_stage.data(), cwt_stage.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
+        T row[kDiagRec];
+        cost_records_pack<T>(1, kDiagRec, w, row);
+        return cwt_fill_rows(cfg.batch, kDiagRec, row);
     }
     int get_diag_cost_problems(int count, const int* idx, double* w) override {
         if (!kDiagCost) return diag_refuse("pddp_get_diag_cost_problems");
         const std::string complaint = diag_records_complaint<T>(count, idx, w, cfg.batch, NX, NU, false);
         if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_get_diag_cost_problems: " + complaint);
         cwt_stage.resize((size_t)count * kDiagRec);
-        if (d_cwt) {
-            for (int i = 0; i < count;) {
-                int j = i + 1;
-                while (j < count && idx[j] == idx[j - 1] + 1) j++;
-                HIPCHK(hipMemcpyAsync(cwt_stage.data() + (size_t)i * kDiagRec, d_cwt + (size_t)idx[i] * kDiagRec, (size_t)(j - i) * kDiagRec * sizeof(T), hipMemcpyDeviceToHost, stream));
-                i = j;
-            }
-            HIPCHK(hipStreamSynchronize(stream));
-        } else if constexpr (kDiagCost) {
+        if (d_cwt.ptr) { if (int rc = cwt_download_rows(count, idx, kDiagRec)) return rc; }
+        else if constexpr (kDiagCost) {
             for (int i = 0; i < count; i++) diag_record_builtin<P, T>(cfg.N, cwt_stage.data() + (size_t)i * kDiagRec);
         }
         for (size_t e = 0; e < (size_t)count * kDiagRec; e++) w[e] = (double)cwt_stage[e];
@@ -715,15 +695,9 @@ struct Solver : SolverBase {
         const size_t out_stride = (size_t)cfg.max_iter + 2;
         const size_t o_state = 0, o_xb = o_state + Bc * sizeof(SolverState<T>), o_u = o_xb + Bc * 2 * N * NX * sizeof(T), o_KT = o_u + Bc * N * NU * sizeof(T),
                      o_J = o_KT + Bc * N * NX * NU * sizeof(T), o_a = o_J + Bc * out_stride * sizeof(T), need_bytes = o_a + Bc * out_stride * sizeof(int) + 16 * Bc;
-        if (h_stage_bytes < need_bytes) {
-            if (h_stage) hipHostFree(h_stage);
-            h_stage = nullptr; h_stage_bytes = 0;
-            HIPCHK(hipHostMalloc((void**)&h_stage, need_bytes, hipHostMallocDefault));
-            h_stage_bytes = need_bytes;
-        }
+        if (int rc = reserve(h_stage, need_bytes, "hipHostMalloc failed for the staging area of the MPC call")) return rc;
         {
-            unsigned char* hi = h_stage;                            // inputs first (the outputs overwrite them after the solve)
-            T* hx = (T*)hi; T* hg = hx + B * NX; int* hs = (int*)(hg + B * NX);
+            T* hx = h_stage.as<T>(); T* hg = hx + B * NX; int* hs = (int*)(hg + B * NX);      // inputs first (the outputs overwrite them after the solve)
             std::memcpy(hx, xActual, B * NX * sizeof(T)); std::memcpy(hg, xGoal, B * NX * sizeof(T)); std::memcpy(hs, shift, B * sizeof(int));
             if (B == Bc) HIPCHK(hipMemcpyAsync(d_xActual, hx, 2 * B * NX * sizeof(T) + B * sizeof(int), hipMemcpyHostToDevice, stream));   // the load kernel moves goals / shifts where the sweeps read them
             else {                                                  // a chunk smaller than the intake area: the three runs lie apart on the device
@@ -732,22 +706,22 @@ struct Solver : SolverBase {
                 HIPCHK(hipMemcpyAsync(d_shift, hs, B * sizeof(int), hipMemcpyHostToDevice, stream));
             }
         }
-        bool split_roll = false;
-        const int tsm = (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0;
         if constexpr (P::PLANT == 4 && INTEG == 1 && sizeof(T) == 4) {                // float arm with a built-in robot model: the warm-start rollout split over two waves
             if (plan.mpc_split_roll) {
-                split_roll = true;
-                if (from) {
-                    if (tl_variant == 0) hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T, 0>), dim3(B), dim3(512), 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
-                    else hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T, 1>), dim3(B), dim3(512), 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
-                }
-                else if (tl_variant == 0) hipLaunchKernelGGL((k_mpc_load<P, INTEG, T, 0>), dim3(B), dim3(512), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
-                else hipLaunchKernelGGL((k_mpc_load<P, INTEG, T, 1>), dim3(B), dim3(512), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
+                if (tl_variant == 0) launch_mpc_load<0>(clear_vars, full_rollout, from, d_idx, from_batch);
+                else launch_mpc_load<1>(clear_vars, full_rollout, from, d_idx, from_batch);
+                return 0;
             }
         }
-        if (!split_roll && from) hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T>), dim3(B), dim3(256), 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
-        else if (!split_roll) hipLaunchKernelGGL((k_mpc_load<P, INTEG, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0);
+        launch_mpc_load<-1>(clear_vars, full_rollout, from, d_idx, from_batch);
         return 0;
+    }
+    // k_mpc_load, or with `from` its slots form, in the form V: the 512-thread pipeline of built-in robot model V = 0 / 1, or (V = -1) the 256-thread kernel
+    template <int V> void launch_mpc_load(int clear_vars, int full_rollout, const Buffers<T>* from, const int* d_idx, int from_batch) {
+        const dim3 grid(cfg.batch), block(V < 0 ? 256 : 512);
+        const int tsm = (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0;
+        if (from) hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T, V>), grid, block, 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
+        else hipLaunchKernelGGL((k_mpc_load<P, INTEG, T, V>), grid, block, 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
     }
     int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) override {
         if (int rc = mpc_enqueue_load("mpc_load", xActual, xGoal, shift, clear_vars, full_rollout)) return rc;
@@ -789,11 +763,11 @@ struct Solver : SolverBase {
             hipLaunchKernelGGL((k_mpc_store<P, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, 1, d_mpc_out, (int)rec_bytes, (int)out_stride);
             HIPCHK(hipGetLastError());
             after_store();
-            HIPCHK(hipMemcpyAsync(h_stage, d_mpc_out, B * rec_bytes, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(h_stage.ptr, d_mpc_out, B * rec_bytes, hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
             hstate.resize(B);
             for (size_t pb = 0; pb < B; pb++) {
-                const unsigned char* r = h_stage + pb * rec_bytes;
+                const unsigned char* r = h_stage.as<unsigned char>() + pb * rec_bytes;
                 std::memcpy(&hstate[pb], r, sizeof(SolverState<T>));
                 const T* rx = reinterpret_cast<const T*>(r + rec_state);
                 if (x) std::memcpy((T*)x + pb * N * NX, rx, N * NX * sizeof(T));
@@ -836,10 +810,10 @@ struct Solver : SolverBase {
     int status(int* done, int* iters) override {
         hstate.resize(cfg.batch);
         const size_t bytes = cfg.batch * sizeof(SolverState<T>);
-        if (!h_state) HIPCHK(hipHostMalloc((void**)&h_state, cap_batch * sizeof(SolverState<T>), hipHostMallocDefault));   // pinned: the poll is one asynchronous copy + one wait
-        HIPCHK(hipMemcpyAsync(h_state, b.state, bytes, hipMemcpyDeviceToHost, stream));
+        if (int rc = reserve(h_state, cap_batch * sizeof(SolverState<T>), "hipHostMalloc failed for the solver states")) return rc;   // pinned: the poll is one asynchronous copy + one wait
+        HIPCHK(hipMemcpyAsync(h_state.ptr, b.state, bytes, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        std::memcpy(hstate.data(), h_state, bytes);
+        std::memcpy(hstate.data(), h_state.ptr, bytes);
         for (int i = 0; i < cfg.batch; i++) { if (done) done[i] = hstate[i].done; if (iters) iters[i] = hstate[i].iter; }
         return 0;
     }
@@ -871,14 +845,12 @@ struct Solver : SolverBase {
     // a refill does not rely on what the area holds: load_problems clears the solver states and the Jout / alphaOut rows of its chunk first.
     Solver* intake = nullptr;
     const Solver* intake_of = nullptr;             // set on the intake itself: the handle it serves
-    int* d_slot_idx = nullptr;                     // [kSlotIntakeMax] the slot indices of the chunk in flight
-    unsigned char* d_slot_stage = nullptr; size_t d_slot_stage_cap = 0;      // pddp_store_problems: the packed rows of one chunk
+    DeviceBuf d_slot_idx;                        // [kSlotIntakeMax] the slot indices of the chunk in flight
+    int* slot_idx() const { return d_slot_idx.as<int>(); }
+    DeviceBuf d_slot_stage;                        // pddp_store_problems: the packed rows of one chunk
     void adopt_selection(const Solver& o) { plan = o.plan; tl_variant = o.tl_variant; tl_grav = o.tl_grav; }
     int slot_chunk() const { return cfg.batch < kSlotIntakeMax ? cfg.batch : kSlotIntakeMax; }
-    int ensure_slot_idx() {
-        if (!d_slot_idx && hipMalloc((void**)&d_slot_idx, kSlotIntakeMax * sizeof(int)) != hipSuccess) return fail(PDDP_ENOMEM, "hipMalloc failed for the slot indices");
-        return 0;
-    }
+    int ensure_slot_idx() { return reserve(d_slot_idx, kSlotIntakeMax * sizeof(int), "hipMalloc failed for the slot indices"); }
     int ensure_intake() {
         // the arrays that exist only on some kernel families must exist on both sides (pddp_set_array("model_*") can move a handle to another family)
         if (intake && ((intake->b.xw != nullptr) != (b.xw != nullptr) || intake->b.xw_rec != b.xw_rec || (intake->b.ABc != nullptr) < (b.ABc != nullptr) ||
@@ -897,7 +869,7 @@ struct Solver : SolverBase {
         in.cw = cw; in.sp = sp; in.dt = dt; in.b.model = b.model; in.h_overridden = h_overridden;
         if (b.cwt && !in.b.cwt) {                                    // per-problem cost weights: the intake area gets a table of its own, filled per chunk from the slots' rows (load_problems)
             if (int rc = in.ensure_cost_table(slot_chunk())) return rc;
-            in.b.cwt = in.d_cwt;
+            in.b.cwt = in.cwt_rows();
         }
         if (!b.ABc) { in.b.ABc = nullptr; in.b.Hc = nullptr; }      // the handle left the compact layouts (ab_keep_reference_layout): so does its intake
         return ensure_slot_idx();
@@ -933,7 +905,7 @@ struct Solver : SolverBase {
         if (cfg.ee_cost) slot_add(fetch, in.b.xTarget, b.xTarget, NX * sizeof(T), NX * sizeof(T), NX * sizeof(T), kSlotCopy);      // the slots' own nominal-state targets: read by the setup kernel, not part of a load
         if (b.cwt) {                                                 // ... and their own cost weights: rows idx[c0 .. c0 + n) of the handle's table -> rows 0 .. n of the intake's
             const size_t rb = table_record_len() * sizeof(T);
-            if (!slot_add(fetch, in.d_cwt, d_cwt, rb, rb, rb, kSlotCopy)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
+            if (!slot_add(fetch, in.cwt_rows(), cwt_rows(), rb, rb, rb, kSlotCopy)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
         }
         const size_t N = cfg.N;
         const int C = slot_chunk();
@@ -941,15 +913,15 @@ struct Solver : SolverBase {
         for (int c0 = 0; c0 < count && !rc; c0 += C) {
             const int n = count - c0 < C ? count - c0 : C;
             in.cfg.batch = n;                                        // this chunk's view of the intake area: launches and transfers cover n problems
-            if (hipMemcpyAsync(d_slot_idx, idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, "pddp_load_problems: index transfer failed"); break; }
-            if (fetch.n) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, fetch.n), dim3(256), 0, stream, fetch, (const int*)d_slot_idx, n, (int)cfg.batch, 1);
+            if (hipMemcpyAsync(slot_idx(), idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, "pddp_load_problems: index transfer failed"); break; }
+            if (fetch.n) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, fetch.n), dim3(256), 0, stream, fetch, (const int*)slot_idx(), n, (int)cfg.batch, 1);
             // what the init path keeps or does not write, as on a fresh handle whatever ran on the intake before (a control cycle of named slots leaves some robot's
             // state and observables there): state.pw = 0, the rows of Jout / alphaOut zero behind element 0
             if (hipMemsetAsync(in.b.state, 0, (size_t)n * sizeof(SolverState<T>), stream) != hipSuccess || hipMemsetAsync(in.b.Jout, 0, (size_t)n * (cfg.max_iter + 2) * sizeof(T), stream) != hipSuccess ||
                 hipMemsetAsync(in.b.alphaOut, 0, (size_t)n * (cfg.max_iter + 2) * sizeof(int), stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, "pddp_load_problems: clearing the intake area failed"); break; }
             rc = in.enqueue_load((const T*)x0 + (size_t)c0 * N * NX, (const T*)u0 + (size_t)c0 * N * NU, (const T*)xg + (size_t)c0 * NX, nullptr, nullptr, nullptr, nullptr, 0, 1,
                                  ignore_first_defect);
-            if (!rc) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, tab.n), dim3(256), 0, stream, tab, (const int*)d_slot_idx, n, (int)cfg.batch, 0);
+            if (!rc) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, tab.n), dim3(256), 0, stream, tab, (const int*)slot_idx(), n, (int)cfg.batch, 0);
         }
         in.cfg.batch = C;
         if (rc) { hipStreamSynchronize(stream); return rc; }
@@ -967,13 +939,8 @@ struct Solver : SolverBase {
         size_t at[6], need = 0;
         for (int k = 0; k < 6; k++) { at[k] = need; if (host[k]) need += ((size_t)C * row[k] + 15) / 16 * 16; }
         if (!need) return 0;
-        if (d_slot_stage_cap < need) {
-            HIPCHK(hipStreamSynchronize(stream));
-            if (d_slot_stage) hipFree(d_slot_stage);
-            d_slot_stage = nullptr; d_slot_stage_cap = 0;
-            if (hipMalloc((void**)&d_slot_stage, need) != hipSuccess) return fail(PDDP_ENOMEM, "pddp_store_problems: hipMalloc failed for the staging buffer");
-            d_slot_stage_cap = need;
-        }
+        if (int rc = reserve(d_slot_stage, need, "pddp_store_problems: hipMalloc failed for the staging buffer")) return rc;
+        unsigned char* const stage = d_slot_stage.as<unsigned char>();
         SlotTable t;
         t.n = 0; t.N = cfg.N; t.state = reinterpret_cast<const unsigned char*>(b.state); t.state_stride = sizeof(SolverState<T>);
         t.off_cur = offsetof(SolverState<T>, cur); t.off_alpha = offsetof(SolverState<T>, alphaIndex);
@@ -981,12 +948,12 @@ struct Solver : SolverBase {
         const size_t sstride[6] = {2 * row[0], row[1], row[2], row[3], row[4], (size_t)cfg.A * e};
         const int op[6] = {kSlotCopyHalf, kSlotCopy, kSlotCopy, kSlotCopy, kSlotCopy, kSlotCopyAlpha};
         int which[6], nw = 0;
-        for (int k = 0; k < 6; k++) if (host[k]) { if (!slot_add(t, d_slot_stage + at[k], src[k], row[k], sstride[k], row[k], op[k])) return fail(PDDP_EINVAL, "pddp_store_problems: internal error (slot table)"); which[nw++] = k; }
+        for (int k = 0; k < 6; k++) if (host[k]) { if (!slot_add(t, stage + at[k], src[k], row[k], sstride[k], row[k], op[k])) return fail(PDDP_EINVAL, "pddp_store_problems: internal error (slot table)"); which[nw++] = k; }
         for (int c0 = 0; c0 < count; c0 += C) {
             const int n = count - c0 < C ? count - c0 : C;
-            HIPCHK(hipMemcpyAsync(d_slot_idx, idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream));
-            hipLaunchKernelGGL((k_slots_gather<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)d_slot_idx, n, (int)cfg.batch);
-            for (int w = 0; w < nw; w++) { const int k = which[w]; HIPCHK(hipMemcpyAsync((unsigned char*)host[k] + (size_t)c0 * row[k], d_slot_stage + at[k], (size_t)n * row[k], hipMemcpyDeviceToHost, stream)); }
+            HIPCHK(hipMemcpyAsync(slot_idx(), idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL((k_slots_gather<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)slot_idx(), n, (int)cfg.batch);
+            for (int w = 0; w < nw; w++) { const int k = which[w]; HIPCHK(hipMemcpyAsync((unsigned char*)host[k] + (size_t)c0 * row[k], stage + at[k], (size_t)n * row[k], hipMemcpyDeviceToHost, stream)); }
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
@@ -999,7 +966,7 @@ struct Solver : SolverBase {
     // what travels in and out per slot: mpc_slots.hpp
     bool cycle_tables(std::vector<SlotTable>& in_t, std::vector<SlotTable>& out_t) {
         const Solver& in = *intake;
-        const MpcSlotSide<T> is{b.cwt ? in.d_cwt : nullptr, in.d_xActual, in.d_goal_in, in.d_shift}, hs{b.cwt ? d_cwt : nullptr, d_xActual, d_goal_in, d_shift};
+        const MpcSlotSide<T> is{b.cwt ? in.cwt_rows() : nullptr, in.d_xActual, in.d_goal_in, in.d_shift}, hs{b.cwt ? cwt_rows() : nullptr, d_xActual, d_goal_in, d_shift};
         return mpc_slot_tables<NX, NU, T>(in_t, out_t, in.b, in.mb, is, b, mb, hs, cfg.N, cfg.M, cfg.A, cfg.max_iter, cfg.ee_cost, table_record_len());
     }
     // pddp_mpc_slots_profile (measurement): HIP events around the in stage (movers + load kernel), the cycle and the out stage of every chunk
@@ -1033,15 +1000,15 @@ struct Solver : SolverBase {
         for (int c0 = 0; c0 < count && !rc; c0 += C) {
             const int n = count - c0 < C ? count - c0 : C;
             in.cfg.batch = n;                                        // this chunk's view of the intake area, as in load_problems
-            if (hipMemcpyAsync(d_slot_idx, idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, std::string(who) + ": index transfer failed"); break; }
+            if (hipMemcpyAsync(slot_idx(), idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, std::string(who) + ": index transfer failed"); break; }
             if (slots_timing) hipEventRecord(slots_ev[0], stream);
-            for (const SlotTable& t : in_t) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)d_slot_idx, n, (int)cfg.batch, 1);
+            for (const SlotTable& t : in_t) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)slot_idx(), n, (int)cfg.batch, 1);
             if ((rc = in.mpc_launch_load((const T*)xActual + (size_t)c0 * NX, (const T*)xGoal + (size_t)c0 * NX, shift + c0, clear_vars, full_rollout, &b,
-                                         d_slot_idx, (int)cfg.batch))) break;
+                                         slot_idx(), (int)cfg.batch))) break;
             if (slots_timing) hipEventRecord(slots_ev[1], stream);
             const auto scatter_out = [&] {
                 if (slots_timing) hipEventRecord(slots_ev[2], stream);
-                for (const SlotTable& t : out_t) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)d_slot_idx, n, (int)cfg.batch, 0);
+                for (const SlotTable& t : out_t) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)slot_idx(), n, (int)cfg.batch, 0);
                 if (slots_timing) hipEventRecord(slots_ev[3], stream);
             };
             if (solve) {
@@ -1143,27 +1110,24 @@ struct Solver : SolverBase {
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
-    // grow-only device scratch of the helper entry points below (owned by the handle: no hipMalloc / hipFree -- an implicit device synchronisation -- per call,
-    // nothing to leak on an error return; released with the handle)
-    void* scratch_buf[3] = {nullptr, nullptr, nullptr}; size_t scratch_cap[3] = {0, 0, 0};
+    // grow-only device scratch of the helper entry points below (owned by the handle: no allocation and release -- an implicit device synchronisation -- per call,
+    // nothing to leak on an error return; released with the handle), never smaller than 4096 bytes
+    DeviceBuf scratch_buf[3];
     int scratch(int slot, size_t bytes, void** out) {
-        if (scratch_cap[slot] < bytes) {
-            if (scratch_buf[slot]) { HIPCHK(hipStreamSynchronize(stream)); hipFree(scratch_buf[slot]); scratch_buf[slot] = nullptr; scratch_cap[slot] = 0; }
-            const size_t cap = bytes < 4096 ? 4096 : bytes;
-            if (hipMalloc(&scratch_buf[slot], cap) != hipSuccess) return fail(PDDP_ENOMEM, "hipMalloc failed for a helper's scratch buffer");
-            scratch_cap[slot] = cap;
-        }
-        *out = scratch_buf[slot];
+        if (int rc = reserve(scratch_buf[slot], bytes, "hipMalloc failed for a helper's scratch buffer", 4096)) return rc;
+        *out = scratch_buf[slot].ptr;
         return 0;
     }
     // ---- lock-step experiment helpers
     using PD = typename P::template Rebind<double>;
-    void* model_d = nullptr;                           // the plant's constants in double (the simulated robot runs in double)
+    const void* model_d = nullptr;                     // the plant's constants in double (the simulated robot runs in double); the block is one of `allocs`
     int ensure_model_d() {
         if (model_d) return 0;
         typename PD::Model hm; fill_model(hm, cfg);
-        HIPCHK(hipMalloc(&model_d, sizeof(hm))); allocs.push_back(model_d);
-        HIPCHK(hipMemcpy(model_d, &hm, sizeof(hm), hipMemcpyHostToDevice));
+        DeviceBuf blk;
+        if (!blk.reserve(sizeof(hm))) return fail(PDDP_ENODEVICE, "hipMalloc failed for the simulated robot's model");
+        HIPCHK(hipMemcpy(blk.ptr, &hm, sizeof(hm), hipMemcpyHostToDevice));
+        model_d = blk.ptr; allocs.push_back(std::move(blk));
         return 0;
     }
     int simulate(const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps, const void* goal, void* xActual,
@@ -1184,7 +1148,7 @@ struct Solver : SolverBase {
         a.x = buf; a.u = buf + nx; a.KT = buf + nx + nu; a.N = cfg.N; a.step_us = step_us(cfg);
         a.t0_us = t0_us; a.elapsed_us = elapsed_us; a.substeps = substeps; a.goal = goal ? buf + nx + nu + nk + NX : nullptr; a.ee_z = cfg.ee_on_link_z;
         a.xActual = buf + nx + nu + nk; a.out = dout;
-        hipLaunchKernelGGL((k_plant_sim<PD, INTEG, T>), dim3(1), dim3(64), 0, stream, (const void*)model_d, a);
+        hipLaunchKernelGGL((k_plant_sim<PD, INTEG, T>), dim3(1), dim3(64), 0, stream, model_d, a);
         HIPCHK(hipGetLastError());
         double ho[2] = {0, 0};
         HIPCHK(hipMemcpyAsync(ho, dout, sizeof(ho), hipMemcpyDeviceToHost, stream));
@@ -1197,9 +1161,9 @@ struct Solver : SolverBase {
     // pddp_simulate_batch: the same body for every problem of the handle, one wavefront each (k_plant_sim_batch).  Its buffers are its own, grow-only and released with
     // the handle -- not the helpers' scratch slots above, not the MPC call's staging: whatever else is enqueued on the stream keeps what it owns.  Per call: one transfer
     // up (the packed per-problem records) + the three plans when they come from the host, one launch, one transfer back (state | error | failed), one synchronisation.
-    unsigned char* d_simb = nullptr; size_t d_simb_cap = 0;          // device: input records, then output records
-    T* d_simb_plan = nullptr; size_t d_simb_plan_cap = 0;            // device: uploaded plans x | u | KT
-    unsigned char* h_simb = nullptr; size_t h_simb_cap = 0;          // pinned: the same two record areas
+    DeviceBuf d_simb_buf;            // device: input records, then output records
+    DeviceBuf d_simb_plan_buf;       // device: uploaded plans x | u | KT
+    PinnedBuf h_simb_buf;            // pinned: the same two record areas
     int simulate_batch(const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us, int substeps, const void* goal, void* xActual,
                        double* avg_err, int* failed) override {
         using In = PlantSimBatchIn<PD, T>; using Out = PlantSimBatchOut<PD, T>;
@@ -1210,26 +1174,14 @@ struct Solver : SolverBase {
         for (size_t i = 0; i < B; i++) if (!(elapsed_us[i] >= 0)) return fail(PDDP_EINVAL, "pddp_simulate_batch: elapsed_us[" + std::to_string(i) + "] must be >= 0");
         if (int mrc = ensure_model_d()) return mrc;
         const size_t in_bytes = (B * sizeof(In) + 15) / 16 * 16, rec_bytes = in_bytes + B * sizeof(Out);
-        if (d_simb_cap < rec_bytes) {
-            HIPCHK(hipStreamSynchronize(stream));
-            if (d_simb) hipFree(d_simb);
-            if (h_simb) hipHostFree(h_simb);
-            d_simb = nullptr; h_simb = nullptr; d_simb_cap = 0; h_simb_cap = 0;
-            if (hipMalloc((void**)&d_simb, rec_bytes) != hipSuccess) return fail(PDDP_ENOMEM, "pddp_simulate_batch: hipMalloc failed for the per-problem records");
-            d_simb_cap = rec_bytes;
-            HIPCHK(hipHostMalloc((void**)&h_simb, rec_bytes, hipHostMallocDefault));
-            h_simb_cap = rec_bytes;
-        }
+        if (int rc = reserve(d_simb_buf, rec_bytes, "pddp_simulate_batch: hipMalloc failed for the per-problem records")) return rc;
+        if (int rc = reserve(h_simb_buf, rec_bytes, "pddp_simulate_batch: hipHostMalloc failed for the per-problem records")) return rc;
+        unsigned char* const d_simb = d_simb_buf.as<unsigned char>(); unsigned char* const h_simb = h_simb_buf.as<unsigned char>();
         const size_t nx = B * N * NX, nu = B * N * NU, nk = B * N * NX * NU;
         const T *px = nullptr, *pu = nullptr, *pKT = nullptr;
         if (x) {
-            if (d_simb_plan_cap < nx + nu + nk) {
-                HIPCHK(hipStreamSynchronize(stream));
-                if (d_simb_plan) hipFree(d_simb_plan);
-                d_simb_plan = nullptr; d_simb_plan_cap = 0;
-                if (hipMalloc((void**)&d_simb_plan, (nx + nu + nk) * sizeof(T)) != hipSuccess) return fail(PDDP_ENOMEM, "pddp_simulate_batch: hipMalloc failed for the uploaded plans");
-                d_simb_plan_cap = nx + nu + nk;
-            }
+            if (int rc = reserve(d_simb_plan_buf, (nx + nu + nk) * sizeof(T), "pddp_simulate_batch: hipMalloc failed for the uploaded plans")) return rc;
+            T* const d_simb_plan = d_simb_plan_buf.as<T>();
             px = d_simb_plan; pu = px + nx; pKT = pu + nu;
             HIPCHK(hipMemcpyAsync(d_simb_plan, x, nx * sizeof(T), hipMemcpyHostToDevice, stream));
             HIPCHK(hipMemcpyAsync(d_simb_plan + nx, u, nu * sizeof(T), hipMemcpyHostToDevice, stream));
@@ -1243,7 +1195,7 @@ struct Solver : SolverBase {
             std::memcpy(r.x, (const T*)xActual + i * NX, NX * sizeof(T));
         }
         HIPCHK(hipMemcpyAsync(d_simb, h_simb, B * sizeof(In), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL((k_plant_sim_batch<PD, INTEG, T>), dim3((unsigned)B), dim3(64), 0, stream, (const void*)model_d, (const In*)d_simb, (Out*)(d_simb + in_bytes), px, pu, pKT, b,
+        hipLaunchKernelGGL((k_plant_sim_batch<PD, INTEG, T>), dim3((unsigned)B), dim3(64), 0, stream, model_d, (const In*)d_simb, (Out*)(d_simb + in_bytes), px, pu, pKT, b,
                            (int)N, step_us(cfg), substeps, goal ? 1 : 0, cfg.ee_on_link_z);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_simb + in_bytes, d_simb + in_bytes, B * sizeof(Out), hipMemcpyDeviceToHost, stream));

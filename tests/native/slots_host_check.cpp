@@ -5,6 +5,7 @@
 #include <cassert>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "slots.hpp"
@@ -79,6 +80,28 @@ int main() {
         for (int k = 0; k < kSlotMaxDesc; k++) assert(slot_add(full, ixb.data(), xb.data(), 4, 4, 4, kSlotCopy));
         assert(!slot_add(full, ixb.data(), xb.data(), 4, 4, 4, kSlotCopy));
         assert(slot_vec((void*)16, (void*)32, 48, 64, 16) == 16 && slot_vec((void*)16, (void*)40, 48, 64, 16) == 8 && slot_vec((void*)16, (void*)32, 48, 64, 12) == 4);
+    }
+    // ---- for_each_slot_run: the runs tile [0, count) in order, the slots inside a run ascend by one, and no run could have taken its successor's first element
+    {
+        const std::vector<std::vector<int>> lists = {{3}, {0, 1, 2, 3}, {5, 0, 1, 2, 4}, {4, 3, 2}, {1, 3, 5}, {0, 1, 7, 8, 9, 2}};
+        const size_t runs_of[6] = {1, 1, 3, 3, 3, 3};
+        for (size_t l = 0; l < lists.size(); l++) {
+            const std::vector<int>& idx = lists[l];
+            std::vector<std::pair<int, int>> runs;
+            for_each_slot_run((int)idx.size(), idx.data(), [&](int first, int len) { runs.push_back({first, len}); });
+            int next = 0;
+            for (size_t r = 0; r < runs.size(); r++) {
+                const int first = runs[r].first, len = runs[r].second;
+                assert(first == next && len >= 1 && first + len <= (int)idx.size());
+                for (int j = first + 1; j < first + len; j++) assert(idx[j] == idx[j - 1] + 1);
+                if (r + 1 < runs.size()) assert(idx[first + len] != idx[first + len - 1] + 1);
+                next = first + len;
+            }
+            assert(next == (int)idx.size() && runs.size() == runs_of[l]);
+        }
+        int calls = 0;
+        for_each_slot_run(0, nullptr, [&](int, int) { calls++; });
+        assert(calls == 0);
     }
     std::printf("slots_host_check: ok\n");
     return 0;
