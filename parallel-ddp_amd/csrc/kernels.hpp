@@ -13,6 +13,7 @@
 #include "bp_mq.hpp"
 #include "kernel_plan.hpp"
 #include "mpc.hpp"
+#include "mpc_record.hpp"
 #include "sim.hpp"
 
 namespace pddp {
@@ -1015,32 +1016,24 @@ __global__ __launch_bounds__(512) void k_mpc_load_slots(Buffers<T> b, MpcBuffers
     mpc_load_body<P, INTEG, T, V, true>(this_wave(), s, b, mb, dm, dt, blockIdx.x, xActual + (size_t)blockIdx.x * P::NX, shift[blockIdx.x], clear_vars, full_rollout,
                                         (int)threadIdx.x >> 6, (int)blockDim.x >> 6, pipe, &prev);
 }
-// out != null: the problem's results packed into one record of rec_bytes for a single transfer back -- [SolverState, padded to 16 bytes][x: current half][u][K]
-// [Jout: out_stride][alphaOut: out_stride ints]; a problem that took no step packs the fall-back arrays it has just been restored from (the same values).
+// out != null: the problem's results packed into one record for a single transfer back (mpc_record.hpp: state | x: current half | u | K | Jout | alphaOut); a problem
+// that took no step packs the fall-back arrays it has just been restored from (the same values).
 template <typename P, typename T>
-__global__ __launch_bounds__(256) void k_mpc_store(Buffers<T> b, MpcBuffers<T> mb, Dims dm, int only_exited, unsigned char* out, int rec_bytes, int out_stride) {
+__global__ __launch_bounds__(256) void k_mpc_store(Buffers<T> b, MpcBuffers<T> mb, Dims dm, int only_exited, unsigned char* out, MpcRecord rec) {
     constexpr int NX = P::NX, NU = P::NU;
     const int pb = blockIdx.x, N = dm.N;
     const SolverState<T> st = b.state[pb];
     const bool skip = only_exited && !st.done;                  // (uniform) a problem that is still iterating keeps its trajectory: the caller goes on with it
     if (!skip && threadIdx.x < 64) mpc_store_body<P, T>(this_wave(), b, mb, dm, pb);          // (wave 0; blocks of 256 threads only pack faster)
     if (!out) return;
-    const int nt = blockDim.x;
-    unsigned char* r = out + (size_t)pb * rec_bytes;
-    if (threadIdx.x == 0) *reinterpret_cast<SolverState<T>*>(r) = st;
+    unsigned char* r = out + (size_t)pb * rec.bytes;
+    if (threadIdx.x == 0) *reinterpret_cast<SolverState<T>*>(r + rec.state) = st;
     if (skip) return;
-    T* rx = reinterpret_cast<T*>(r + (sizeof(SolverState<T>) + 15) / 16 * 16);
     const bool old = !st.took_step;
     const T* xs = old ? mb.x_old + (size_t)pb * N * NX : b.xb + ((size_t)pb * 2 + st.cur) * N * NX;
     const T* us = old ? mb.u_old + (size_t)pb * N * NU : b.ucur + (size_t)pb * N * NU;
     const T* ks = old ? mb.KT_old + (size_t)pb * N * NX * NU : b.KT + (size_t)pb * N * NX * NU;
-    for (int e = threadIdx.x; e < N * NX; e += nt) rx[e] = xs[e];
-    rx += N * NX;
-    for (int e = threadIdx.x; e < N * NU; e += nt) rx[e] = us[e];
-    rx += N * NU;
-    for (int e = threadIdx.x; e < N * NX * NU; e += nt) rx[e] = ks[e];
-    rx += N * NX * NU;
-    for (int e = threadIdx.x; e < out_stride; e += nt) { rx[e] = b.Jout[(size_t)pb * out_stride + e]; reinterpret_cast<int*>(rx + out_stride)[e] = b.alphaOut[(size_t)pb * out_stride + e]; }
+    mpc_record_pack<T>(rec, r, threadIdx.x, blockDim.x, xs, us, ks, b.Jout + (size_t)pb * rec.out_stride, b.alphaOut + (size_t)pb * rec.out_stride);
 }
 
 // initial cost + solver state: grid (B), block 64, dynamic LDS N*sizeof(T).

@@ -8,6 +8,7 @@
 #include "cost_table.hpp"
 #include "diag_cost_table.hpp"
 #include "mpc_slots.hpp"
+#include "mpc_record.hpp"
 #include "tl_launch.hpp"
 #include "mx_launch.hpp"
 
@@ -152,9 +153,10 @@ struct Solver : SolverBase {
         int rc = for_each_array<NX, NU>(c, b, mb, arrays, [this](const char* name, auto** out, size_t count) { return alloc(name, out, count); });
         if (rc) return rc;
         // MPC inputs of a control cycle in ONE device run (one transfer): measured states | goals | shifts
-        if ((rc = alloc("mpc_in", &d_xActual, 2 * B * NX + B * sizeof(int) / sizeof(T) + 2))) return rc;
-        d_goal_in = d_xActual + B * NX; d_shift = reinterpret_cast<int*>(d_goal_in + B * NX);
-        arrays["xActual"] = {d_xActual, B * NX * sizeof(T)}; arrays["shift"] = {d_shift, B * sizeof(int)};      // the views the facade's GPUVars name (MPCHelpers.hpp)
+        const MpcInputRun in = mpc_input_run(sizeof(T), NX, B);
+        if ((rc = alloc("mpc_in", &d_xActual, in.elems))) return rc;
+        d_goal_in = mpc_at<T>(d_xActual, in.goal); d_shift = mpc_at<int>(d_xActual, in.shift);
+        arrays["xActual"] = {d_xActual, in.x_bytes}; arrays["shift"] = {d_shift, in.shift_bytes};     // the views the facade's GPUVars name (MPCHelpers.hpp)
         std::vector<T> al(A);
         alpha_table(c, al.data());
         HIPCHK(hipMemcpy(b.alpha, al.data(), A * sizeof(T), hipMemcpyHostToDevice));
@@ -690,21 +692,19 @@ struct Solver : SolverBase {
     // (k_mpc_load_slots: an intake area loading named slots of its handle); the kernel form is selected the same way for both.
     int mpc_launch_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, const Buffers<T>* from = nullptr,
                         const int* d_idx = nullptr, int from_batch = 0) {
-        const size_t B = cfg.batch, Bc = cap_batch, N = cfg.N;
-        // one pinned staging area: pageable host memory would make every small transfer of the cycle a synchronous staging copy of its own
-        const size_t out_stride = (size_t)cfg.max_iter + 2;
-        const size_t o_state = 0, o_xb = o_state + Bc * sizeof(SolverState<T>), o_u = o_xb + Bc * 2 * N * NX * sizeof(T), o_KT = o_u + Bc * N * NU * sizeof(T),
-                     o_J = o_KT + Bc * N * NX * NU * sizeof(T), o_a = o_J + Bc * out_stride * sizeof(T), need_bytes = o_a + Bc * out_stride * sizeof(int) + 16 * Bc;
-        if (int rc = reserve(h_stage, need_bytes, "hipHostMalloc failed for the staging area of the MPC call")) return rc;
-        {
-            T* hx = h_stage.as<T>(); T* hg = hx + B * NX; int* hs = (int*)(hg + B * NX);      // inputs first (the outputs overwrite them after the solve)
-            std::memcpy(hx, xActual, B * NX * sizeof(T)); std::memcpy(hg, xGoal, B * NX * sizeof(T)); std::memcpy(hs, shift, B * sizeof(int));
-            if (B == Bc) HIPCHK(hipMemcpyAsync(d_xActual, hx, 2 * B * NX * sizeof(T) + B * sizeof(int), hipMemcpyHostToDevice, stream));   // the load kernel moves goals / shifts where the sweeps read them
-            else {                                                  // a chunk smaller than the intake area: the three runs lie apart on the device
-                HIPCHK(hipMemcpyAsync(d_xActual, hx, B * NX * sizeof(T), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipMemcpyAsync(d_goal_in, hg, B * NX * sizeof(T), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipMemcpyAsync(d_shift, hs, B * sizeof(int), hipMemcpyHostToDevice, stream));
-            }
+        const size_t B = cfg.batch, Bc = cap_batch;
+        // one pinned staging area: pageable host memory would make every small transfer of the cycle a synchronous staging copy of its own.  It holds the input run,
+        // then the result records (mpc_record.hpp) that overwrite it after the solve
+        const MpcInputRun in = mpc_input_run(sizeof(T), NX, B);
+        const size_t out_bytes = Bc * mpc_record_of<T>(NX, NU, cfg.N, (size_t)cfg.max_iter + 2).bytes, in_bytes = mpc_input_run(sizeof(T), NX, Bc).bytes;
+        if (int rc = reserve(h_stage, out_bytes > in_bytes ? out_bytes : in_bytes, "hipHostMalloc failed for the staging area of the MPC call")) return rc;
+        unsigned char* h = h_stage.as<unsigned char>();
+        std::memcpy(h + in.x, xActual, in.x_bytes); std::memcpy(h + in.goal, xGoal, in.x_bytes); std::memcpy(h + in.shift, shift, in.shift_bytes);
+        if (B == Bc) HIPCHK(hipMemcpyAsync(d_xActual, h, in.bytes, hipMemcpyHostToDevice, stream));   // the load kernel moves goals / shifts where the sweeps read them
+        else {                                                  // a chunk smaller than the intake area: the three runs lie apart on the device
+            HIPCHK(hipMemcpyAsync(d_xActual, h + in.x, in.x_bytes, hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_goal_in, h + in.goal, in.x_bytes, hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_shift, h + in.shift, in.shift_bytes, hipMemcpyHostToDevice, stream));
         }
         if constexpr (P::PLANT == 4 && INTEG == 1 && sizeof(T) == 4) {                // float arm with a built-in robot model: the warm-start rollout split over two waves
             if (plan.mpc_split_roll) {
@@ -742,67 +742,54 @@ struct Solver : SolverBase {
     template <typename AfterStore>
     int mpc_cycle(double t0, int ifd, int max_iter, double budget_ms, int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters,
                   AfterStore&& after_store) {
-        const size_t B = cfg.batch, N = cfg.N;
-        const size_t out_stride = (size_t)cfg.max_iter + 2;
-        const size_t rec_state = (sizeof(SolverState<T>) + 15) / 16 * 16;
-        const size_t rec_bytes = (rec_state + (N * NX + N * NU + N * NX * NU + out_stride) * sizeof(T) + out_stride * sizeof(int) + 15) / 16 * 16;   // <= the six separate areas' share per problem
-        const int saved_max_iter = sp.max_iter;
+        const size_t B = cfg.batch;
+        const MpcRecord rec = mpc_record_of<T>(NX, NU, cfg.N, (size_t)cfg.max_iter + 2);
+        struct Restore { int& v; const int saved; ~Restore() { v = saved; } } limit{sp.max_iter, sp.max_iter};      // this call's iteration limit, until the function returns
         sp.max_iter = max_iter;                                  // acceptRejectTrajGPU(..., max_iter)
         launch_init_cost_and_setup(stream, ifd, 0, 1);
         HIPCHK(hipGetLastError());
-        std::vector<int> done(B);
         int rc = 0;
         const int chunk = poll_every > 0 ? poll_every : 4;
+        bool all_exited = false;
         if (budget_ms <= 0 && chunk >= max_iter) {
             // no time budget and the whole iteration limit in one chunk: every problem is done after max_iter sweeps whatever happens (the limit forces the exit), so
             // nothing has to be polled -- sweeps, fall-back kernel and ALL result transfers are enqueued back to back and the cycle synchronises once
-            if ((rc = iterate(max_iter))) { sp.max_iter = saved_max_iter; return rc; }
-            sp.max_iter = saved_max_iter;
-            // k_mpc_store also packs every problem's results (state | x | u | K | J | step sizes) into one device run: ONE transfer back instead of six
-            if (!d_mpc_out) { int arc = alloc("mpc_out", &d_mpc_out, cap_batch * rec_bytes); if (arc) return arc; }
-            hipLaunchKernelGGL((k_mpc_store<P, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, 1, d_mpc_out, (int)rec_bytes, (int)out_stride);
+            if ((rc = iterate(max_iter))) return rc;
+            // k_mpc_store also packs every problem's results into one device run of records: ONE transfer back instead of six
+            if (!d_mpc_out) { int arc = alloc("mpc_out", &d_mpc_out, cap_batch * rec.bytes); if (arc) return arc; }
+            hipLaunchKernelGGL((k_mpc_store<P, T>), dim3(B), dim3(256), 0, stream, b, mb, dm, 1, d_mpc_out, rec);
             HIPCHK(hipGetLastError());
             after_store();
-            HIPCHK(hipMemcpyAsync(h_stage.ptr, d_mpc_out, B * rec_bytes, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(h_stage.ptr, d_mpc_out, B * rec.bytes, hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
             hstate.resize(B);
+            all_exited = true;
             for (size_t pb = 0; pb < B; pb++) {
-                const unsigned char* r = h_stage.as<unsigned char>() + pb * rec_bytes;
-                std::memcpy(&hstate[pb], r, sizeof(SolverState<T>));
-                const T* rx = reinterpret_cast<const T*>(r + rec_state);
-                if (x) std::memcpy((T*)x + pb * N * NX, rx, N * NX * sizeof(T));
-                if (u) std::memcpy((T*)u + pb * N * NU, rx + N * NX, N * NU * sizeof(T));
-                if (KT) std::memcpy((T*)KT + pb * N * NX * NU, rx + N * NX + N * NU, N * NX * NU * sizeof(T));
-                if (Jout) std::memcpy((T*)Jout + pb * out_stride, rx + N * NX + N * NU + N * NX * NU, out_stride * sizeof(T));
-                if (alphaOut) std::memcpy(alphaOut + pb * out_stride, rx + N * NX + N * NU + N * NX * NU + out_stride, out_stride * sizeof(int));
+                mpc_record_unpack<T>(rec, h_stage.as<unsigned char>() + pb * rec.bytes, pb, hstate.data(), (T*)x, (T*)u, (T*)KT, (T*)Jout, alphaOut);
+                all_exited &= (hstate[pb].done != 0);
             }
-            bool all_exited = true;
-            for (size_t i = 0; i < B; i++) all_exited &= (hstate[i].done != 0);
-            if (all_exited) {
-                for (size_t i = 0; i < B; i++) { if (success) success[i] = hstate[i].took_step; if (iters) iters[i] = hstate[i].iter; }
-                return 0;
+        }
+        // (after the single synchronisation too: a sweep whose backward pass failed raises rho and repeats without advancing `iter` (backwardPassGPU's retry loop,
+        // bpHelpers.cuh:497-511): such a problem is still running after max_iter sweeps -- go on in the polled loop, like the reference would)
+        if (!all_exited) {
+            std::vector<int> done(B);
+            bool fresh = false;
+            for (int guard = 0; guard < 100000; guard++) {
+                if (budget_ms > 0 && now_ms() - t0 > budget_ms) break;   // time_budget (MPCHelpers.cuh:919,941,1001): checked between chunks of sweeps
+                fresh = false;
+                if ((rc = iterate(chunk))) break;
+                if ((rc = status(done.data(), nullptr))) break;
+                fresh = true;                                            // hstate reflects everything enqueued so far
+                bool all = true;
+                for (int v : done) all &= (v != 0);
+                if (all) break;
             }
-            // a sweep whose backward pass failed raises rho and repeats without advancing `iter` (backwardPassGPU's retry loop, bpHelpers.cuh:497-511): such a
-            // problem is still running after max_iter sweeps -- go on in the polled loop below, like the reference would
-            sp.max_iter = max_iter;
+            if (rc) return rc;
+            hipLaunchKernelGGL((k_mpc_store<P, T>), dim3(B), dim3(64), 0, stream, b, mb, dm, 0, (unsigned char*)nullptr, MpcRecord{});   // copies only: the states status() fetched above stay valid
+            HIPCHK(hipGetLastError());
+            after_store();
+            if ((rc = store_impl(x, u, KT, Jout, alphaOut, nullptr, fresh))) return rc;
         }
-        bool fresh = false;
-        for (int guard = 0; guard < 100000; guard++) {
-            if (budget_ms > 0 && now_ms() - t0 > budget_ms) break;   // time_budget (MPCHelpers.cuh:919,941,1001): checked between chunks of sweeps
-            fresh = false;
-            if ((rc = iterate(chunk))) break;
-            if ((rc = status(done.data(), nullptr))) break;
-            fresh = true;                                            // hstate reflects everything enqueued so far
-            bool all = true;
-            for (int v : done) all &= (v != 0);
-            if (all) break;
-        }
-        sp.max_iter = saved_max_iter;
-        if (rc) return rc;
-        hipLaunchKernelGGL((k_mpc_store<P, T>), dim3(B), dim3(64), 0, stream, b, mb, dm, 0, (unsigned char*)nullptr, 0, 0);   // copies only: the states status() fetched above stay valid
-        HIPCHK(hipGetLastError());
-        after_store();
-        if ((rc = store_impl(x, u, KT, Jout, alphaOut, nullptr, fresh))) return rc;
         for (size_t i = 0; i < B; i++) { if (success) success[i] = hstate[i].took_step; if (iters) iters[i] = hstate[i].iter; }
         return 0;
     }
