@@ -264,6 +264,37 @@ int pddp_diag_cost_size(pddp_handle h);
 int pddp_set_diag_cost(pddp_handle h, const double* w /* [record] */);
 int pddp_set_diag_cost_problems(pddp_handle h, int count, const int* idx, const double* w /* [count][record] */);
 int pddp_get_diag_cost_problems(pddp_handle h, int count, const int* idx, double* w /* [count][record] */);
+/* Per-knot goal trajectories of the pendulum, cart-pole and quadrotor (plants 1-3), per problem.  A problem either has a goal trajectory
+ * G[N][n] in the handle's element type, or it has none.
+ *   with a trajectory: every place where the cost, its gradient or the initial cost of knot k reads the goal reads G[k] instead of
+ *     xGoal -- running knots k < N-1 and the final knot k = N-1 (with the qf weights).  k is the ABSOLUTE knot index of the horizon, not
+ *     an index inside a shooting segment: g_k = [q .* (x_k - G[k]); r .* u_k], cost 1/2 (sum q_i (x_k - G[k])_i^2 + sum r_j u_j^2); at the
+ *     final knot qf and G[N-1].  H_k does not depend on the goal and is unchanged; the backward pass, the linear sweeps and the line
+ *     search read no goal.
+ *   without one: the problem behaves as it always did and reads xGoal[b] at every knot.
+ * The array "xGoal" is untouched by these calls: it keeps what the loads and control cycles put there and pddp_get_array("xGoal") returns
+ * that; for a problem with a trajectory the cost simply does not read it.
+ * Timing is that of pddp_set_cost_problems / pddp_set_diag_cost_problems: a trajectory is in force for the following loads and solves; H, g
+ * and the cost of a trajectory already in a slot are NOT rebuilt by the setter; problems that are not named keep theirs; running problems
+ * in other slots are untouched.  The first setter call gives the handle a device table [batch][N][n] in its element type and a flag per
+ * problem; a handle without a table of diagonal cost records gets one as well, every row the built-in record (as by the first
+ * pddp_set_diag_cost_problems: pddp_get_diag_cost_problems keeps returning the built-in record); the captured sweep graph is dropped
+ * once.  Later calls only write rows and flags (on the solver's stream, one synchronisation before the call returns).  A handle that
+ * never calls the setter launches exactly the kernels and arguments it launches without these entry points.
+ * Control cycles (pddp_mpc_solve, pddp_mpc_solve_problems, pddp_mpc_load*): the library does NOT shift a goal trajectory.  The rows are
+ * the goals of the NEW horizon's knots 0..N-1 as they stand when the cycle starts; a caller that tracks a moving window writes the new
+ * window with the setter before the cycle (count * N * n numbers of upload).  pddp_load_problems / pddp_mpc_solve_problems /
+ * pddp_mpc_load_problems run the named slots with their own trajectories; a cycle does not change a trajectory.
+ * pddp_get_goal_trajectory_problems returns the stored rows and has[i] = 1 for a problem with a trajectory; for a problem without one
+ * (and for every problem before the first setter call) that problem's xGoal repeated N times and has[i] = 0.  has may be NULL.
+ * pddp_clear_goal_trajectory_problems: the named problems read xGoal again (from the next load / solve on, as above); on a handle that
+ * never had a trajectory a successful no-op.
+ * PDDP_EINVAL, with the handle unchanged: plants 4 and 5; count < 1; a NULL idx or G; an index outside [0, batch); an index named twice;
+ * (setter) a value that is not finite in the handle's element type.  The handle need not be loaded yet. */
+int pddp_goal_trajectory_size(pddp_handle h);                                   /* N * n */
+int pddp_set_goal_trajectory_problems(pddp_handle h, int count, const int* idx, const void* G /* [count][N][n], handle dtype */);
+int pddp_get_goal_trajectory_problems(pddp_handle h, int count, const int* idx, void* G /* [count][N][n] */, int* has /* [count], may be NULL */);
+int pddp_clear_goal_trajectory_problems(pddp_handle h, int count, const int* idx);
 /* ---- the lock-step experiment around the solver ------------------------- */
 /* simulateForward<T, SUBSTEPS> (examples/WAFR_MPC_examples.cu:111-139): the simulated robot of the lock-step MPC experiment.  Starting
  * from xActual at plant time t0_us (the plan's t0), integrates the plant IN DOUBLE for elapsed_us in `substeps` steps under the trajectory

@@ -124,7 +124,7 @@ PDDP_HD void nis_body(const Wave& w, NisScratch<P, INTEG, T>& s, const Buffers<T
         wsync();
     }
     P::load_model(w, s.plant, reinterpret_cast<const typename P::Model*>(b.model));
-    nis_knot<P, INTEG, T>(w, s, dm, k, xc, uc, b.xGoal + (size_t)pb * NX, cw, dt,
+    nis_knot<P, INTEG, T>(w, s, dm, k, xc, uc, goal_at(problem_goal<P, T>(b, pb, N), k), cw, dt,      // (a goal trajectory: row k of the problem's own base and stride, plants.hpp)
                           b.AB + ((size_t)pb * N + k) * NX * NM, b.H + ((size_t)pb * N + k) * NM * NM, b.g + ((size_t)pb * N + k) * NM,
                           b.xTarget + (size_t)pb * NX, b.tshift[pb], mode == 1 ? b.costk + (size_t)pb * N + k : nullptr, mode == 1);
 }
@@ -143,10 +143,10 @@ PDDP_HD void init_cost_body(const Wave& w, T* cost_k, const Buffers<T>& b, const
     constexpr int NX = P::NX, NU = P::NU;
     const int N = dm.N;
     const T* x = b.xb + ((size_t)pb * 2 + 0) * N * NX; const T* u = b.ucur + (size_t)pb * N * NU;
-    const T* xg = b.xGoal + (size_t)pb * NX;
+    const auto xg = problem_goal<P, T>(b, pb, N);                 // (a pointer, or base and stride of the problem's goal trajectory: plants.hpp)
     T J = 0;
     if (stage == 0) {
-        PDDP_FOR(k, N) cost_k[k] = P::cost(cw, x + (size_t)k * NX, u + (size_t)k * NU, xg, k, N);
+        PDDP_FOR(k, N) cost_k[k] = P::cost(cw, x + (size_t)k * NX, u + (size_t)k * NU, goal_at(xg, k), k, N);
         wsync();
         J = tree_sum<T>(w, cost_k, N);
     } else if (stage == 2) {

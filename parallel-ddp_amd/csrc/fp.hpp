@@ -86,9 +86,10 @@ PDDP_HD void rollout_seed_from_candidate(const Wave& w, const Dims& dm, const Fp
 // Nonlinear rollout of segment bInd.  Start state: a.segx[bInd] (from the sweep), or xcur[0] for segment 0.
 // Writes x[k+1], u[k] for the segment's knots and the boundary defect.  cost_k (optional, LDS [N]) receives the
 // per-knot cost of every knot this segment owns.
-template <typename P, int INTEG, typename T, typename CW = CostWeights<T>>      // CW: the record as the plant's cost routines take it (plants.hpp DiagCostWeights for a DiagTab plant)
+// G: the problem's goal as problem_goal (plants.hpp) gives it -- a pointer, or base + stride of a per-knot goal trajectory; goal_at(xg, kn) is the goal of the ABSOLUTE knot kn
+template <typename P, int INTEG, typename T, typename CW = CostWeights<T>, typename G = const T*>      // CW: the record as the plant's cost routines take it (plants.hpp DiagCostWeights for a DiagTab plant)
 PDDP_HD void forward_sim_segment(const Wave& w, SimScratch<P, T>& s, const Dims& dm, const FpArgs<T>& a, int bInd,
-                                 const CW& cw, const T* xg, T* cost_k) {
+                                 const CW& cw, G xg, T* cost_k) {
     constexpr int NX = P::NX, NU = P::NU;
     const int NBk = dm.NB, kStart = bInd * NBk;
     bool ee = false;
@@ -113,7 +114,7 @@ PDDP_HD void forward_sim_segment(const Wave& w, SimScratch<P, T>& s, const Dims&
             s.u[r] = uv; a.u[NU * kn + r] = uv;
         }
         wsync();
-        if (!ee && cost_k && w.lane == 0) cost_k[kn] = P::cost(cw, s.x, s.u, xg, kn, dm.N);
+        if (!ee && cost_k && w.lane == 0) cost_k[kn] = P::cost(cw, s.x, s.u, goal_at(xg, kn), kn, dm.N);
         integrator_step<P, INTEG>(w, s.plant, s.integ, s.xn, s.x, s.u, a.dt);
         if constexpr (P::PLANT == 4) {
             if (ee && (k < NBk - 1 || bInd == dm.M - 1)) {    // not on the "final" state of a non-final segment (:259-265)
@@ -146,7 +147,7 @@ PDDP_HD void forward_sim_segment(const Wave& w, SimScratch<P, T>& s, const Dims&
         const int kn = dm.N - 1;
         PDDP_FOR(r, NU) { const T uv = a.ucur[NU * kn + r]; s.u[r] = uv; a.u[NU * kn + r] = uv; }
         wsync();
-        if (cost_k && w.lane == 0) { cost_k[kn] = P::cost(cw, s.x, s.u, xg, kn, dm.N); a.dnorm[bInd] = 0; }
+        if (cost_k && w.lane == 0) { cost_k[kn] = P::cost(cw, s.x, s.u, goal_at(xg, kn), kn, dm.N); a.dnorm[bInd] = 0; }
         wsync();
     }
 }

@@ -78,7 +78,7 @@ __global__ void k_fp(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int init_ro
     P::load_model(w, sim.plant, reinterpret_cast<const typename P::Model*>(b.model));
     if constexpr (IsDiagTab<P>::value) {                               // the problem's own diagonal (pb is blockIdx.y: a uniform row, scalar loads)
         const DiagCostWeights<T> own = diag_cost_weights(cw, b.cwt + (size_t)pb * P::REC);
-        forward_sim_segment<P, INTEG, T>(w, sim, dm, a, wave_id, own, b.xGoal + (size_t)pb * P::NX, cost_k);
+        forward_sim_segment<P, INTEG, T>(w, sim, dm, a, wave_id, own, problem_goal<P, T>(b, pb, dm.N), cost_k);      // (a goal trajectory: base and stride, the segment's knots are absolute)
     } else forward_sim_segment<P, INTEG, T>(w, sim, dm, a, wave_id, cw, b.xGoal + (size_t)pb * P::NX, cost_k);
     __syncthreads();
     bool ee = false;
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(64) void k_fp_ts(Buffers<T> b, Dims dm, CostWeights
     P::load_model(w, sim.plant, reinterpret_cast<const typename P::Model*>(b.model));
     if constexpr (IsDiagTab<P>::value) {                               // this thread's problem's row: every weight is read where a knot's cost uses it
         const DiagCostWeights<T> own = diag_cost_weights(cw, b.cwt + (size_t)pb * P::REC);
-        for (int bInd = 0; bInd < dm.M; bInd++) forward_sim_segment<P, INTEG, T>(w, sim, dm, a, bInd, own, b.xGoal + (size_t)pb * P::NX, cost_k);
+        for (int bInd = 0; bInd < dm.M; bInd++) forward_sim_segment<P, INTEG, T>(w, sim, dm, a, bInd, own, problem_goal<P, T>(b, pb, dm.N), cost_k);
     } else {
         for (int bInd = 0; bInd < dm.M; bInd++) forward_sim_segment<P, INTEG, T>(w, sim, dm, a, bInd, cw, b.xGoal + (size_t)pb * P::NX, cost_k);
     }
@@ -283,7 +283,7 @@ struct FpCfStage {
     static constexpr int PW = 64 / A, NX = P::NX, NU = P::NU;
     union {
         struct { T M[PW][NX * NX], xp[PW][NX], Bdu[PW][NX], d[PW][NX]; } sw;
-        struct { T K[PW][NX * NU], xp[PW][NX], up[PW][NU], du[PW][NU]; } ro;
+        struct { T K[PW][NX * NU], xp[PW][NX], up[PW][NU], du[PW][NU], xg[PW][NX]; } ro;      // xg: the knot's goal, travelling with xp (a GoalTab plant only; the sweep's half of the union is the larger one)
     };
 };
 template <typename T, int PW, int L>
@@ -421,6 +421,18 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
     // (one in-order vmcnt), and a dozen registers' worth of addresses and values kept alive across the three dynamics evaluations
     { const int p = lane / NX, q = (pb0 + p < batch) ? pb0 + p : batch - 1; if (lane < PW * NX) (&goal_s[0][0])[lane] = b.xGoal[(size_t)q * NX + (lane - p * NX)]; }
     const T* xg = goal_s[grp];
+    // a per-knot goal trajectory (GoalTab, plants.hpp) travels the way the nominal state does: the xlane lanes fetch their element of knot k + 1's goal one step ahead and
+    // write it into the stage next to xp; the cost of step k reads sc.ro.xg.  Both stages start out holding xGoal, and only the lanes of a flagged problem overwrite
+    // their element, so an unflagged problem in the same wavefront reads xGoal at every knot.  Every lane issues the load (a lane without a share reads a valid
+    // address of the wave's problems and drops the value, as the other fetches do): one resource on the wave's first problem's block, one 32-bit offset per lane.
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t r_gt; [[maybe_unused]] unsigned gt_off = 0; [[maybe_unused]] bool gt_on = false; [[maybe_unused]] T rxg = T(0);
+    if constexpr (IsGoalTab<P>::value && PART == 1) {
+        const int p = lane / NX, q = (pb0 + p < batch) ? pb0 + p : batch - 1, e = lane - p * NX;
+        r_gt = mx_rsrc(b.gtab + (size_t)pb0 * N * NX);
+        gt_off = (unsigned)(((size_t)(q - pb0) * N * NX + e) * sizeof(T));
+        gt_on = lane < PW * NX && b.gflag[q] != 0;
+        if (lane < PW * NX) { const T v = b.xGoal[(size_t)q * NX + e]; (&stage[0].ro.xg[0][0])[lane] = v; (&stage[1].ro.xg[0][0])[lane] = v; }
+    }
     const T alpha = b.alpha[a_idx];
     // the current trajectory sits in one half of xb per PROBLEM (state.cur): this lane's share of the state fetch is entry e of problem p
     const __amdgpu_buffer_rsrc_t r_xcur = mx_rsrc(b.xb + (size_t)pb0 * 2 * N * NX);
@@ -495,11 +507,13 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
         rxp = mx_bld<T>(r_xcur, xcur_off, (unsigned)k * (unsigned)(NX * sizeof(T)));
         fp_cf_fetch<T, PW, NU>(rup, lU, r_up, k);
         fp_cf_fetch<T, PW, NU>(rdu, lU, r_du, k);
+        if constexpr (IsGoalTab<P>::value) rxg = mx_bld<T>(r_gt, gt_off, (unsigned)k * (unsigned)(NX * sizeof(T)));
     };
     auto put = [&](FpCfStage<P, T, A>& sg) {
         fp_cf_put<T, PW, NX * NU>(rK, &sg.ro.K[0][0], lane);
         if (xlane) (&sg.ro.xp[0][0])[lane] = rxp;
         fp_cf_put<T, PW, NU>(rup, &sg.ro.up[0][0], lane); fp_cf_put<T, PW, NU>(rdu, &sg.ro.du[0][0], lane);
+        if constexpr (IsGoalTab<P>::value) { if (gt_on) (&sg.ro.xg[0][0])[lane] = rxg; }
     };
     fetch(0); put(stage[0]); wsync();
     T cost_k[kTsMaxN];
@@ -520,7 +534,8 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
             uv -= alpha * sc.ro.du[grp][r] + Kdx;
             u[r] = uv;
         }
-        cost_k[k] = P::cost(cw, x, u, xg, k, N);
+        if constexpr (IsGoalTab<P>::value) cost_k[k] = P::cost(cw, x, u, sc.ro.xg[grp], k, N);      // knot k's goal, from the stage
+        else cost_k[k] = P::cost(cw, x, u, xg, k, N);
         cf_integrator_step<P, INTEG, T>(xn, x, u, dt);
         put(stage[(k + 1) & 1]); wsync();
         T rec[REC];                                         // this knot's record: the state the step started from and its control
@@ -543,7 +558,8 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
         PDDP_UNROLL for (int i = 0; i < NX; i++) rec[i] = x[i];
         PDDP_UNROLL for (int r = 0; r < NU; r++) rec[NX + r] = u[r];
         if (live) cf_bst_vec<T, REC>(r_rec, rec_off, (unsigned)(N - 1) * rstr, rec);
-        cost_k[N - 1] = P::cost(cw, x, u, xg, N - 1, N);
+        if constexpr (IsGoalTab<P>::value) cost_k[N - 1] = P::cost(cw, x, u, sc.ro.xg[grp], N - 1, N);      // (stage (N - 1) & 1 holds row N - 1)
+        else cost_k[N - 1] = P::cost(cw, x, u, xg, N - 1, N);
         dmx = tmax(dmx, T(0));
     }
     if (!live) return;
@@ -641,6 +657,7 @@ __global__ __launch_bounds__(64) void k_bp_gl(Buffers<T> b, Dims dm, int batch) 
 template <typename P> struct GradZeroCols { static constexpr unsigned value = 0u; };                                    // bit c: column c of dynamicsGradient's dqdd is identically zero
 template <typename T> struct GradZeroCols<QuadPlant<T>> { static constexpr unsigned value = 0x1C7u; };                  // x y z and their rates (plants/dynamics_quad.cuh:75-169 never writes them; tests/test_closed_form_pins.py)
 template <typename B, typename T> struct GradZeroCols<DiagTab<B, T>> : GradZeroCols<B> {};                               // (the same dynamics)
+template <typename B, typename T> struct GradZeroCols<GoalTab<B, T>> : GradZeroCols<B> {};
 template <typename P> struct GradCols {
     static constexpr int NM = P::NX + P::NU;
     static constexpr unsigned zero = GradZeroCols<P>::value;
@@ -691,7 +708,7 @@ __global__ __launch_bounds__(64) void k_nis_kb(Buffers<T> b, Dims dm, CostWeight
                 }
                 if (mode == 1 || !st.done) {
                     if (do_g) {
-                        const T* xg = b.xGoal + (size_t)pb * NX;
+                        const T* xg = goal_at(problem_goal<P, T>(b, pb, N), k);      // (a goal trajectory: the row of (pb, k))
                         T* gk = b.g + ((size_t)pb * N + k) * NM;
                         if constexpr (P::kPluginCost) P::cost_grad(cw, b.H + ((size_t)pb * N + k) * NM * NM, gk, x, u, xg, k, N);
                         else {

@@ -131,6 +131,15 @@ extern "C" int pddp_diag_cost_size(pddp_handle h) {
 extern "C" int pddp_set_diag_cost(pddp_handle h, const double* w) { IMPL(h); return s->set_diag_cost(w); }
 extern "C" int pddp_set_diag_cost_problems(pddp_handle h, int count, const int* idx, const double* w) { IMPL(h); return s->set_diag_cost_problems(count, idx, w); }
 extern "C" int pddp_get_diag_cost_problems(pddp_handle h, int count, const int* idx, double* w) { IMPL(h); return s->get_diag_cost_problems(count, idx, w); }
+// per-knot goal trajectories of the same plants (goal_traj_table.hpp)
+extern "C" int pddp_goal_trajectory_size(pddp_handle h) {
+    IMPL(h);
+    const int len = s->goal_trajectory_size();
+    return len ? len : fail(PDDP_EINVAL, "pddp_goal_trajectory_size: goal trajectories belong to the pendulum, cart-pole and quadrotor (plants 1-3)");
+}
+extern "C" int pddp_set_goal_trajectory_problems(pddp_handle h, int count, const int* idx, const void* G) { IMPL(h); return s->set_goal_trajectory_problems(count, idx, G); }
+extern "C" int pddp_get_goal_trajectory_problems(pddp_handle h, int count, const int* idx, void* G, int* has) { IMPL(h); return s->get_goal_trajectory_problems(count, idx, G, has); }
+extern "C" int pddp_clear_goal_trajectory_problems(pddp_handle h, int count, const int* idx) { IMPL(h); return s->clear_goal_trajectory_problems(count, idx); }
 extern "C" int pddp_simulate(pddp_handle h, const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps, const void* goal_xyz,
                              void* xActual_inout, double* avg_err, int* failed) {
     IMPL(h); if (!x || !u || !KT || !xActual_inout) return fail(PDDP_EINVAL, "null argument");

@@ -272,6 +272,32 @@ PDDP_HD T knot_weight(const Buffers<T>& b, const CostWeights<T>& cw, int pb, int
     else return P::weight(cw, i, k, N);
 }
 
+// ---- per-knot goal trajectories of the same plants (pddp_set_goal_trajectory_problems) ----
+// Buffers::gtab is null, or a table [batch][N][NX] with a flag per problem (Buffers::gflag): a flagged problem's cost of knot k is taken against row k of its block, an
+// unflagged one's against xGoal[pb] as always.  GoalTab<B, T> is DiagTab<B, T> -- the same cost routines, the same record -- for the handles that have such a table: a
+// policy of its own again, so that the instantiations on B and on DiagTab<B, T> are the ones they always were and see none of this.  What differs is WHERE the goal
+// pointer handed to cost() / cost_grad() comes from: problem_goal gives a problem's goal as a base and a stride (NX for a flagged problem, 0 otherwise), goal_at the
+// knot's row.  Branch-free: a wavefront may hold problems with and without a trajectory.  On every other policy problem_goal is the pointer xGoal + pb NX and goal_at
+// returns it.
+template <typename B, typename T>
+struct GoalTab : DiagTab<B, T> {
+    template <typename U> using Rebind = GoalTab<typename B::template Rebind<U>, U>;
+};
+template <typename B, typename T> struct IsDiagTab<GoalTab<B, T>> { static constexpr bool value = true; };
+template <typename P> struct IsGoalTab { static constexpr bool value = false; };
+template <typename B, typename T> struct IsGoalTab<GoalTab<B, T>> { static constexpr bool value = true; };
+template <typename T>
+struct GoalRows { const T* base; int stride; };
+template <typename T> PDDP_HD const T* goal_at(const T* g, int) { return g; }
+template <typename T> PDDP_HD const T* goal_at(const GoalRows<T>& g, int k) { return g.base + (size_t)k * g.stride; }      // k: the ABSOLUTE knot of the horizon
+template <typename P, typename T>
+PDDP_HD auto problem_goal(const Buffers<T>& b, int pb, int N) {
+    if constexpr (IsGoalTab<P>::value) {
+        const bool on = b.gflag[pb] != 0;
+        return GoalRows<T>{on ? b.gtab + (size_t)pb * N * P::NX : b.xGoal + (size_t)pb * P::NX, on ? P::NX : 0};
+    } else return (const T*)(b.xGoal + (size_t)pb * P::NX);
+}
+
 // A scalar plug-in's gradient routine also returns qdd; the kernel families build the midpoint / RK3 stage states from that qdd (serial paths) or from the dynamics routine's
 // (the staged three-lane path of integrators.hpp), so the two have to be the SAME numbers -- the reference's plug-ins call dynamics() inside dynamicsGradient.  Checked on the
 // host instantiation when a handle of a user plant is created.

@@ -79,6 +79,11 @@ struct SolverBase {
     virtual int set_diag_cost(const double* w) = 0;
     virtual int set_diag_cost_problems(int count, const int* idx, const double* w) = 0;
     virtual int get_diag_cost_problems(int count, const int* idx, double* w) = 0;
+    // per-knot goal trajectories of the same plants (goal_traj_table.hpp); G in the handle's element type, checked by the handle
+    virtual int goal_trajectory_size() const = 0;  // N NX; 0: the handle's plant has no goal trajectories (plants 4 and 5)
+    virtual int set_goal_trajectory_problems(int count, const int* idx, const void* G) = 0;
+    virtual int get_goal_trajectory_problems(int count, const int* idx, void* G, int* has) = 0;
+    virtual int clear_goal_trajectory_problems(int count, const int* idx) = 0;
     virtual int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
                           int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) = 0;
     virtual int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) = 0;   // mpc_solve's load stage alone (teacher-forcing hook)

@@ -7,6 +7,7 @@
 #include "slots.hpp"
 #include "cost_table.hpp"
 #include "diag_cost_table.hpp"
+#include "goal_traj_table.hpp"
 #include "mpc_slots.hpp"
 #include "mpc_record.hpp"
 #include "tl_launch.hpp"
@@ -400,15 +401,15 @@ struct Solver : SolverBase {
                 const bool fu = plan.mq_fused && (!store_candidates || fused_hook);      // (the phase hook's backward pass writes A - B K / B du: its sweep is teacher-forced from them)
                 const bool dh = !P::kPluginCost && !h_overridden;   // the plant's own diagonal cost Hessian: not read
                 // (only the instantiations that take the running knots' Hessian from the weights differ with a table of diagonal records: the others read H)
-                if (dh && fu) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
-                else if (dh) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
+                if (dh && fu) with_weight_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
+                else if (dh) with_weight_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
                 else if (fu) hipLaunchKernelGGL((k_bp_mq<P, T, false, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
                 else hipLaunchKernelGGL((k_bp_mq<P, T, false>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
             }
             break;
         case kBpCl:
             if constexpr (P::PLANT != 4 && P::NX == 12 && P::NU == 4)
-                with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_cl<Q, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, cw, (int)B, (!P::kPluginCost && !h_overridden) ? 1 : 0); });
+                with_weight_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_cl<Q, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, cw, (int)B, (!P::kPluginCost && !h_overridden) ? 1 : 0); });
             break;
         case kBpGl:
             if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) {
@@ -615,7 +616,16 @@ struct Solver : SolverBase {
     static constexpr int kDiagRec = 2 * NX + NU;
     int diag_cost_size() const override { return kDiagCost ? kDiagRec : 0; }
     // f(plant policy): DiagTab<P, T> for a handle with a table of diagonal records, P otherwise (the arm's per-problem weights are a run-time branch inside its kernels)
+    // and GoalTab<P, T> for one that also has a table of goal trajectories (the kernels that evaluate the cost or its gradient: they read the goal)
     template <typename F> void with_cost_plant(F&& f) {
+        if constexpr (kDiagCost) {
+            if (b.gtab) { f(GoalTab<P, T>{}); return; }
+            if (b.cwt) { f(DiagTab<P, T>{}); return; }
+        }
+        f(P{});
+    }
+    // the same for the kernels that only take the running knots' Hessian from the weights (k_bp_mq, k_bp_cl): they read no goal, so a goal table changes nothing for them
+    template <typename F> void with_weight_plant(F&& f) {
         if constexpr (kDiagCost) { if (b.cwt) { f(DiagTab<P, T>{}); return; } }
         f(P{});
     }
@@ -663,6 +673,97 @@ struct Solver : SolverBase {
             for (int i = 0; i < count; i++) diag_record_builtin<P, T>(cfg.N, cwt_stage.data() + (size_t)i * kDiagRec);
         }
         for (size_t e = 0; e < (size_t)count * kDiagRec; e++) w[e] = (double)cwt_stage[e];
+        return 0;
+    }
+    // ---- per-knot goal trajectories of the same plants (goal_traj_table.hpp, plants.hpp GoalTab): pddp_set_goal_trajectory_problems / pddp_get_... / pddp_clear_...
+    // A table [batch][N][NX] and a flag per problem, from the first setter call on; b.gtab / b.gflag are what the kernels see.  With them every kernel that evaluates the
+    // cost or its gradient runs in its GoalTab instantiation (with_cost_plant); a flagged problem's knot k reads row k of its block, an unflagged one xGoal.  A handle with
+    // goal trajectories always has the table of diagonal records too (GoalTab is layered on DiagTab), created through ensure_diag_table with the built-in rows.
+    DeviceBuf d_gtab, d_gflag;
+    T* gtab_rows() const { return d_gtab.template as<T>(); }
+    int* gflag_rows() const { return d_gflag.template as<int>(); }
+    std::vector<T> gt_stage;                       // host rows of the getter call in flight
+    std::vector<int> gf_stage;                     // host flags of the call in flight
+    size_t goal_len() const { return (size_t)cfg.N * NX; }
+    int goal_trajectory_size() const override { return kDiagCost ? (int)goal_len() : 0; }
+    int goal_refuse(const char* who) { return fail(PDDP_EINVAL, std::string(who) + ": goal trajectories belong to the pendulum, cart-pole and quadrotor (plants 1-3)"); }
+    // room for `rows` problems, flags cleared; the kernels do not see it yet
+    int reserve_goal_table(int rows) {
+        if (int rc = reserve(d_gtab, (size_t)rows * goal_len() * sizeof(T), "hipMalloc failed for the goal trajectories")) return rc;
+        if (int rc = reserve(d_gflag, (size_t)rows * sizeof(int), "hipMalloc failed for the goal trajectories' flags")) return rc;
+        HIPCHK(hipMemsetAsync(d_gtab.ptr, 0, (size_t)rows * goal_len() * sizeof(T), stream));
+        HIPCHK(hipMemsetAsync(d_gflag.ptr, 0, (size_t)rows * sizeof(int), stream));
+        return 0;
+    }
+    // first setter call: the cost table if there is none, the goal table, no problem flagged; b.gtab / b.gflag; the captured graph goes once (other kernels, other arguments)
+    int ensure_goal_table() {
+        if (b.gtab) return 0;
+        if constexpr (kDiagCost) {
+            if (int rc = ensure_diag_table()) return rc;
+            if (int rc = reserve_goal_table(cfg.batch)) return rc;
+            HIPCHK(hipStreamSynchronize(stream));                   // (nothing in flight reads the old argument set)
+            if (fp_lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fp<GoalTab<P, T>, INTEG, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp_lds));
+            b.gtab = gtab_rows(); b.gflag = gflag_rows();
+            drop_graph();
+        }
+        return 0;
+    }
+    // flag `on` for the named problems, on the stream (gf_stage stays alive until the caller has waited for it)
+    int goal_flags_upload(int count, const int* idx, int on) {
+        gf_stage.assign((size_t)count, on);
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int len) {
+            if (e == hipSuccess) e = hipMemcpyAsync(gflag_rows() + idx[first], gf_stage.data() + first, (size_t)len * sizeof(int), hipMemcpyHostToDevice, stream);
+        });
+        return e == hipSuccess ? 0 : fail(PDDP_ENODEVICE, std::string("goal trajectories: transfer of flags failed: ") + hipGetErrorString(e));
+    }
+    int set_goal_trajectory_problems(int count, const int* idx, const void* Gv) override {
+        if (!kDiagCost) return goal_refuse("pddp_set_goal_trajectory_problems");
+        const T* G = static_cast<const T*>(Gv);
+        const std::string complaint = goal_rows_complaint<T>(count, idx, G, cfg.batch, cfg.N, NX);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_goal_trajectory_problems: " + complaint);
+        if (int rc = ensure_goal_table()) return rc;
+        const size_t len = goal_len();
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int run) {     // contiguous runs of slots in one transfer each; problems that are not named keep theirs
+            if (e == hipSuccess) e = hipMemcpyAsync(gtab_rows() + (size_t)idx[first] * len, G + (size_t)first * len, (size_t)run * len * sizeof(T), hipMemcpyHostToDevice, stream);
+        });
+        if (e != hipSuccess) { hipStreamSynchronize(stream); return fail(PDDP_ENODEVICE, std::string("pddp_set_goal_trajectory_problems: transfer of rows failed: ") + hipGetErrorString(e)); }
+        const int rc = goal_flags_upload(count, idx, 1);
+        HIPCHK(hipStreamSynchronize(stream));
+        return rc;
+    }
+    int clear_goal_trajectory_problems(int count, const int* idx) override {
+        if (!kDiagCost) return goal_refuse("pddp_clear_goal_trajectory_problems");
+        const std::string complaint = goal_rows_complaint<T>(count, idx, nullptr, cfg.batch, cfg.N, NX, false);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_clear_goal_trajectory_problems: " + complaint);
+        if (!b.gtab) return 0;                                      // never had a trajectory: every problem reads xGoal already
+        const int rc = goal_flags_upload(count, idx, 0);
+        HIPCHK(hipStreamSynchronize(stream));
+        return rc;
+    }
+    int get_goal_trajectory_problems(int count, const int* idx, void* Gv, int* has) override {
+        if (!kDiagCost) return goal_refuse("pddp_get_goal_trajectory_problems");
+        T* G = static_cast<T*>(Gv);
+        const std::string complaint = goal_rows_complaint<T>(count, idx, G, cfg.batch, cfg.N, NX, true, false);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_get_goal_trajectory_problems: " + complaint);
+        const size_t len = goal_len();
+        gt_stage.resize((size_t)count * NX);                        // the named problems' xGoal
+        gf_stage.assign((size_t)count, 0);
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int run) {
+            if (e == hipSuccess) e = hipMemcpyAsync(gt_stage.data() + (size_t)first * NX, b.xGoal + (size_t)idx[first] * NX, (size_t)run * NX * sizeof(T), hipMemcpyDeviceToHost, stream);
+            if (b.gtab) {
+                if (e == hipSuccess) e = hipMemcpyAsync(G + (size_t)first * len, gtab_rows() + (size_t)idx[first] * len, (size_t)run * len * sizeof(T), hipMemcpyDeviceToHost, stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(gf_stage.data() + first, gflag_rows() + idx[first], (size_t)run * sizeof(int), hipMemcpyDeviceToHost, stream);
+            }
+        });
+        const hipError_t es = hipStreamSynchronize(stream);
+        if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string("pddp_get_goal_trajectory_problems: transfer failed: ") + hipGetErrorString(e != hipSuccess ? e : es));
+        for (int i = 0; i < count; i++) {
+            if (!gf_stage[i]) goal_rows_from_xgoal<T>(gt_stage.data() + (size_t)i * NX, cfg.N, NX, G + (size_t)i * len);      // no trajectory: what the cost reads, xGoal at every knot
+            if (has) has[i] = gf_stage[i] ? 1 : 0;
+        }
         return 0;
     }
     // The load stage of a control cycle, enqueued: argument checks, pinned staging, the single input transfer and the k_mpc_load launch.  pddp_mpc_solve goes on
@@ -858,6 +959,10 @@ struct Solver : SolverBase {
             if (int rc = in.ensure_cost_table(slot_chunk())) return rc;
             in.b.cwt = in.cwt_rows();
         }
+        if (b.gtab && !in.b.gtab) {                                  // goal trajectories: the same, rows and flags of the chunk's slots
+            if (int rc = in.reserve_goal_table(slot_chunk())) return rc;
+            in.b.gtab = in.gtab_rows(); in.b.gflag = in.gflag_rows();
+        }
         if (!b.ABc) { in.b.ABc = nullptr; in.b.Hc = nullptr; }      // the handle left the compact layouts (ab_keep_reference_layout): so does its intake
         return ensure_slot_idx();
     }
@@ -893,6 +998,11 @@ struct Solver : SolverBase {
         if (b.cwt) {                                                 // ... and their own cost weights: rows idx[c0 .. c0 + n) of the handle's table -> rows 0 .. n of the intake's
             const size_t rb = table_record_len() * sizeof(T);
             if (!slot_add(fetch, in.cwt_rows(), cwt_rows(), rb, rb, rb, kSlotCopy)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
+        }
+        if (b.gtab) {                                                // ... and their goal trajectories: block and flag of slot idx[c0 + i] -> problem i of the intake's table
+            const size_t gb = goal_len() * sizeof(T);
+            if (!slot_add(fetch, in.gtab_rows(), gtab_rows(), gb, gb, gb, kSlotCopy) || !slot_add(fetch, in.gflag_rows(), gflag_rows(), sizeof(int), sizeof(int), sizeof(int), kSlotCopy))
+                return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
         }
         const size_t N = cfg.N;
         const int C = slot_chunk();
@@ -953,7 +1063,9 @@ struct Solver : SolverBase {
     // what travels in and out per slot: mpc_slots.hpp
     bool cycle_tables(std::vector<SlotTable>& in_t, std::vector<SlotTable>& out_t) {
         const Solver& in = *intake;
-        const MpcSlotSide<T> is{b.cwt ? in.cwt_rows() : nullptr, in.d_xActual, in.d_goal_in, in.d_shift}, hs{b.cwt ? cwt_rows() : nullptr, d_xActual, d_goal_in, d_shift};
+        const bool gt = b.gtab != nullptr;
+        const MpcSlotSide<T> is{b.cwt ? in.cwt_rows() : nullptr, in.d_xActual, in.d_goal_in, in.d_shift, gt ? in.gtab_rows() : nullptr, gt ? in.gflag_rows() : nullptr},
+                             hs{b.cwt ? cwt_rows() : nullptr, d_xActual, d_goal_in, d_shift, gt ? gtab_rows() : nullptr, gt ? gflag_rows() : nullptr};
         return mpc_slot_tables<NX, NU, T>(in_t, out_t, in.b, in.mb, is, b, mb, hs, cfg.N, cfg.M, cfg.A, cfg.max_iter, cfg.ee_cost, table_record_len());
     }
     // pddp_mpc_slots_profile (measurement): HIP events around the in stage (movers + load kernel), the cycle and the out stage of every chunk

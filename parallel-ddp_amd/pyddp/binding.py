@@ -369,6 +369,47 @@ class Solver:
         self._chk(self.lib.pddp_get_diag_cost_problems(self.h, idx.size, _p(idx), _p(w)))
         return w
 
+    def has_goal_trajectory(self):
+        """True for the plants whose problems can carry a per-knot goal trajectory (pendulum, cart-pole, quadrotor): set_goal_trajectory_problems /
+        get_goal_trajectory_problems / clear_goal_trajectory_problems."""
+        return self.cfg.plant in (1, 2, 3)
+
+    def goal_trajectory_size(self):
+        """pddp_goal_trajectory_size: N * n numbers per problem, the goals G[N][n] of the horizon's knots; plants 1-3 only."""
+        self.lib.pddp_goal_trajectory_size.argtypes = [C.c_void_p]
+        rc = self.lib.pddp_goal_trajectory_size(self.h)
+        if rc <= 0:
+            self._chk(rc if rc else -1)
+        return rc
+
+    def set_goal_trajectory_problems(self, idx, G):
+        """pddp_set_goal_trajectory_problems: trajectory i of G (len(idx) x N x n numbers, any shape; converted to the handle's element type) for slot idx[i]: its cost
+        reads G[i][k] at knot k instead of xGoal.  In force for the following loads and solves (follow it with load() or load_problems(idx, ...)); the other slots keep
+        theirs.  Control cycles do not shift the rows: write the new window before the cycle."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        G = self.arr(G).ravel()
+        if G.size != idx.size * self.goal_trajectory_size():
+            raise PddpError(f"set_goal_trajectory_problems: {idx.size} slots need {idx.size * self.goal_trajectory_size()} numbers ({self.goal_trajectory_size()} per trajectory), got {G.size}")
+        self.lib.pddp_set_goal_trajectory_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_goal_trajectory_problems(self.h, idx.size, _p(idx), _p(G)))
+
+    def get_goal_trajectory_problems(self, idx):
+        """pddp_get_goal_trajectory_problems: (G [len(idx)][N][n] in the handle's element type, has [len(idx)] int32).  has[i] = 1: slot idx[i] has a trajectory and G[i]
+        is its rows; 0: it has none and G[i] is its xGoal at every knot."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        G = np.zeros((idx.size, self.cfg.N, self.n), self.dtype)
+        has = np.zeros(idx.size, np.int32)
+        self.goal_trajectory_size()                       # (raises for plants 4 and 5 before the shapes above mean anything)
+        self.lib.pddp_get_goal_trajectory_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_get_goal_trajectory_problems(self.h, idx.size, _p(idx), _p(G), _p(has)))
+        return G, has
+
+    def clear_goal_trajectory_problems(self, idx):
+        """pddp_clear_goal_trajectory_problems: the named slots read xGoal again, from the next load or solve on; a no-op on a handle that never had a trajectory."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        self.lib.pddp_clear_goal_trajectory_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(self.lib.pddp_clear_goal_trajectory_problems(self.h, idx.size, _p(idx)))
+
     def solve(self, x0, u0, xGoal, clear_vars=1, ignore_first_defect=1, max_sweeps=None, chunk=8, **load_kw):
         """load -> iterate until every problem has exited -> store (the shape of runiLQR_GPU)."""
         self.load(x0, u0, xGoal, clear_vars, ignore_first_defect, **load_kw)
