@@ -82,8 +82,12 @@ typedef struct pddp_config {
     int use_finite_diff;  /* USE_FINITE_DIFF (config.cuh:68): [A B] of the Euler step by central differences of the plant's `dynamics`, column by column
                            * (finiteDiffInner, DDPHelpers/nisInitHelpers.cuh:138-183) instead of the analytic gradient.  Euler only, joint-space cost. */
     double finite_diff_epsilon; /* FINITE_DIFF_EPSILON (config.cuh:69-71), default 0.00001 */
-    int boundary_cost_to_go_only; /* 0 (default) = the reference: every backward pass leaves the cost-to-go P, p of EVERY knot in the device arrays (d_P, d_p;
-                           * the MPC warm start shifts the whole arrays, MPCHelpers.cuh:602-655).  1 = throughput option of the matrix-core backward pass: only the
+    int boundary_cost_to_go_only; /* 0 (default) = the reference as a caller sees it: whenever a call that enqueues sweeps (pddp_iterate, pddp_solve, pddp_mpc_solve ...) has
+                           * returned, the device arrays hold the cost-to-go P, p of EVERY knot of every problem's last backward pass (d_P, d_p; the MPC warm start
+                           * shifts the whole arrays, MPCHelpers.cuh:602-655) and of the pass before it (Pp, pp).  With tol_cost <= 0 and no negative cost weight the
+                           * matrix-core backward pass leaves the interior slots out in the sweeps in front of a call's last two, for every problem that cannot exit
+                           * within two sweeps (max_iter, maximum rho) -- the same bits after the call, fewer stores.
+                           * 1 = throughput option of the matrix-core backward pass: no sweep writes them, only the
                            * slot in front of every block's first knot is written -- the only ones a later pass reads (the reference's d_Pp / d_pp boundary slots);
                            * the interior cost-to-go is not an output of runiLQR_GPU.  A handle that iterated with 1 refuses a warm-started pddp_mpc_solve
                            * (clear_vars = 0) until a solve has run with every slot kept. */

@@ -549,10 +549,13 @@ __device__ __forceinline__ void mx_lds_knot(MxKnotIn<float, FS, true>& k, unsign
 // One (problem, block of knots).  lds: kMxLds = 400 elements of this wave.  FS: M > 1 (write the forward-sweep operands A - B K, B du).
 // DIAGH: the cost Hessian of every running knot is the joint-space cost's diag(Q1 x 7, Q2 x 7, R x 7) (plants/cost_arm.cuh:158-202, ArmPlant::weight):
 // the setup kernel wrote exactly those numbers into H, so they are taken from the launch arguments (hq1, hq2, hr) and H is not read in the loop.
-// CAB: [A B] comes from the compact array b.ABc (ab_compact.hpp; dt rebuilds the constant rows).  keepP = 0: only the cost-to-go slots a later pass reads are
-// written -- the one in front of the block's first knot, which the neighbouring block's next pass starts from (the reference's d_Pp / d_pp boundary slots); the
-// per-knot P, p of the interior are by-products nobody reads (not an output of runiLQR_GPU; pddp_config.boundary_cost_to_go_only).  The default, the phase hook
-// and MPC handles (whose warm start shifts the whole array, MPCHelpers.cuh:602-655) pass keepP = 1.
+// CAB: [A B] comes from the compact array b.ABc (ab_compact.hpp; dt rebuilds the constant rows).  keepP = 0 (a LEAN pass): only the cost-to-go slots a later pass
+// reads are written -- the one in front of the block's first knot, which the neighbouring block's next pass starts from (the reference's d_Pp / d_pp boundary slots).
+// The per-knot P, p of the interior are read by no pass, but a caller can read them (pddp_get_array, pddp_store; the MPC warm start shifts the whole arrays,
+// MPCHelpers.cuh:602-655) -- BOTH halves of the double buffer, that is the interiors of a problem's last TWO passes, and only between two calls that enqueue sweeps.
+// So the last two sweeps of such a call and the phase hook pass kMxKeepP; the sweeps in front of them pass kMxLeanIfRunning instead, and the pass then decides per
+// problem (may_exit_within_two, solver_state.hpp): it stays lean only where the problem provably runs on through this sweep AND the next, so that neither of its last two passes is
+// ever a lean one.  Handles with pddp_config.boundary_cost_to_go_only pass neither flag: every pass lean, interior slots stale.
 // flags bit 1 (kMxFuseSweep): the block also composes its shooting segment's effect on the forward sweep's two sequences -- with G_k = [A - B K, B du; 0, 1] (15 x 15)
 // the segment's map is Psi = G_last ... G_first, and Psi' <- G_k' Psi' is one more mfma4 per knot on tiles this pass holds anyway (Psi' again in accumulator layout) --
 // and leaves Psi' in b.segmap[problem][block] (256 elements) INSTEAD of writing A - B K and B du of every knot (107 KB per problem, and the linear sweep kernel that would
@@ -570,13 +573,16 @@ __device__ __forceinline__ void mx_store_gain_pieces(const mx_u4& w, __amdgpu_bu
     else if (lane == 26) { mx_u3 t; t[0] = w[0]; t[1] = w[1]; t[2] = w[2]; __builtin_amdgcn_raw_buffer_store_b96(t, rdu, 16u, sod, 0); }
 }
 constexpr int kMxGainStores = 4, kMxCtgStores = 3;                    // store instructions per knot of the prefetching (compact [A B], float) variants: K rows 2g, 2g + 1 and du(2g), du(2g + 1) | [P | p] as 16-byte pieces
+// flags of the pass: bits 0, 1 as named here; bit 2 (kMxLeanIfRunning) with bit 3 (kMxMaxRhoExit) and the call's iteration limit from bit kMxMaxIterShift up are
+// defined beside the rule that reads them, may_exit_within_two (solver_state.hpp: host code, held on the CPU by tests/native/ctg_lean_rule_host_check.cpp)
 constexpr int kMxKeepP = 1, kMxFuseSweep = 2, kMxLds = 400, kMxDmaFloats = 2 * 5 * 64 + 256 + 112;     // (float handles: two operand buffers of five 64-dword regions + the staging areas of [P | p] and of [K | du])
 template <typename T, bool FS, bool DIAGH, bool CAB, bool FUSE, bool HQQ = false>
 __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int pb, int blk, T hq1, T hq2, T hr, T dt, int flags) {
     static_assert(!HQQ || DIAGH, "the compact position block rides on the diagonal-Hessian path");
     using X = Mx<T>;
     using mx4 = mx4t<T>;
-    const int keepP = flags & kMxKeepP;
+    // (wave-uniform: the state record is read through the scalar cache)
+    const int keepP = (flags & kMxKeepP) || ((flags & kMxLeanIfRunning) && may_exit_within_two(b.state[pb], flags));
     const bool fuse = FUSE && blk < dm.M - 1;                          // (the last block's segment has no boundary after it)
     constexpr int NX = 14, NU = 7, NM = 21, SZP = NX * NX, SZAB = NX * NM, SZH = NM * NM;
     const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15, u0 = 2 * g, sc = mx_state<T>(c);      // sc: the state (14: the vector) of this lane's column
@@ -986,6 +992,8 @@ __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int
             T* dJexp = b.dJexp + (size_t)pb * 2 * dm.M;
             dJexp[2 * blk] = a0; dJexp[2 * blk + 1] = a1;
             b.err[(size_t)pb * dm.M + blk] = 0;                       // the generic 7x7 inversion never reports failure (utils/cudaUtils.h:291)
+            // (may_exit_within_two counts on this being the pass's ONLY value of err: a reported failure leaves state.pw unflipped and can end the problem through
+            // bp_retries, neither of which the rule foresees -- a pass that reports failures must not be launched with kMxLeanIfRunning)
         }
     }
 }

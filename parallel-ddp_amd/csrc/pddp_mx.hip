@@ -70,9 +70,10 @@ static void launch_one(hipStream_t s, unsigned n, const Buffers<double>& b, cons
 }
 
 template <typename T>
-void launch_bp_mfma(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batch, bool diag_h, T hq1, T hq2, T hr, T dt, bool keep_P, bool fuse_sweep, int ee) {
+void launch_bp_mfma(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batch, bool diag_h, T hq1, T hq2, T hr, T dt, bool keep_P, bool fuse_sweep, int ee, const SolverParams* lean_if_running) {
     const unsigned n = (unsigned)batch * dm.M;
-    const int kp = (keep_P ? kMxKeepP : 0) | ((fuse_sweep && b.segmap) ? kMxFuseSweep : 0);
+    int kp = (keep_P ? kMxKeepP : 0) | ((fuse_sweep && b.segmap) ? kMxFuseSweep : 0);
+    if (!keep_P && lean_if_running) kp |= kMxLeanIfRunning | (lean_if_running->ignore_max_rho_exit ? 0 : kMxMaxRhoExit) | lean_flags_max_iter(lean_if_running->max_iter);
     const bool cab = b.ABc != nullptr && diag_h;
 #define PDDP_MX_LAUNCH(FS, DH, CB, FU) launch_one<FS, DH, CB, FU>(s, n, b, dm, batch, hq1, hq2, hr, dt, kp, ee)
     const bool fu = (kp & kMxFuseSweep) != 0;
@@ -94,8 +95,8 @@ void launch_bp_mfma(hipStream_t s, const Buffers<T>& b, const Dims& dm, int batc
     }
 #undef PDDP_MX_LAUNCH
 }
-template void launch_bp_mfma<float>(hipStream_t, const Buffers<float>&, const Dims&, int, bool, float, float, float, float, bool, bool, int);
-template void launch_bp_mfma<double>(hipStream_t, const Buffers<double>&, const Dims&, int, bool, double, double, double, double, bool, bool, int);
+template void launch_bp_mfma<float>(hipStream_t, const Buffers<float>&, const Dims&, int, bool, float, float, float, float, bool, bool, int, const SolverParams*);
+template void launch_bp_mfma<double>(hipStream_t, const Buffers<double>&, const Dims&, int, bool, double, double, double, double, bool, bool, int, const SolverParams*);
 
 // k_sweep_maps: grid ceil(B / PER), block 64.  The forward sweep from the per-segment maps the backward pass composed (bp_mfma.hpp kMxFuseSweep): e <- Phi_s e + gamma_s over the
 // segments for the s-sequence (gamma = the map's column 14) and the t-sequence (gamma = the defect of the segment's boundary knot: it enters at the segment's last

@@ -51,7 +51,10 @@ struct Solver : SolverBase {
     }
     void derive_tl_model(const EmptyModel&) {}
     // pddp_set_array("model_I" / "model_F"): re-derive what the kernels take from the model tables as launch arguments
-    void drop_graph() override { if (graph) { hipGraphExecDestroy(graph); graph = nullptr; graph_mode = -1; } if (graph_n) { hipGraphExecDestroy(graph_n); graph_n = nullptr; } }
+    void drop_graph() override {
+        for (hipGraphExec_t* g : {&graph, &graph_lean, &graph_n, &graph_n_lean}) if (*g) { hipGraphExecDestroy(*g); *g = nullptr; }
+        graph_mode = -1;
+    }
     int ab_view(int to_compact) override {
         if constexpr (P::PLANT == 4) {
             if (b.ABc) { launch_abc_convert<T>(stream, b, (int)(cfg.batch * cfg.N), cfg.N, dt, to_compact); HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(stream)); }
@@ -106,7 +109,18 @@ struct Solver : SolverBase {
     bool lean_ctg_ran = false;     // sweeps ran that left the interior cost-to-go slots unwritten (config.boundary_cost_to_go_only): a warm-started MPC call would shift stale slots
     // every knot's P, p written (the reference's d_P / d_p) unless the caller opted out; MPC handles always keep them (MPCHelpers.cuh:602-655 shifts the whole arrays)
     bool keep_all_ctg() const { return !cfg.boundary_cost_to_go_only || cfg.mpc_mode || mpc_used; }
-    hipGraphExec_t graph = nullptr;
+    // The interior slots can only be looked at between two calls that enqueue sweeps, and what is there to see are the two halves of the double buffer: the interiors
+    // of every problem's last two passes.  So the last kKeepSweeps sweeps of a call write them and the sweeps in front are lean for every problem that provably runs on
+    // for two more sweeps (mx_launch.hpp; the pass checks max_iter and the maximum rho per problem).  The exit by tolerance cannot be foreseen, so it has to be
+    // impossible: tol_cost <= 0 and a cost that is never negative (no negative weight; a table of per-problem weights is not looked through) -- a relative decrease
+    // dJ / prevJ of an accepted step is then never below the tolerance.  Matrix-core backward pass of a handle that keeps every slot; everything else runs one kind of sweep.
+    static constexpr int kKeepSweeps = 2;
+    bool split_sweeps() const {
+        const T w[] = {cw.Q1, cw.Q2, cw.R, cw.QF1, cw.QF2, cw.Q_EE1, cw.Q_EE2, cw.QF_EE1, cw.QF_EE2, cw.R_EE, cw.Q_xEE, cw.QF_xEE, cw.Q_xdEE, cw.QF_xdEE};
+        for (T v : w) if (!(v >= T(0))) return false;
+        return plan.bp_mfma && keep_all_ctg() && !(sp.tol_cost > 0.0) && !b.cwt;
+    }
+    hipGraphExec_t graph = nullptr, graph_lean = nullptr;      // one keeping sweep | one lean sweep (split_sweeps() only)
     int graph_mode = -1;
     size_t fp_lds = 0;
 
@@ -377,7 +391,8 @@ struct Solver : SolverBase {
         }
     }
     // fused_hook: pddp_run_phase(PDDP_PHASE_BP_FUSED), the hook's backward pass composing the sweep maps as production's does
-    void launch_bp(hipStream_t s, int store_candidates, bool fused_hook = false) {
+    // lean: a sweep of split_sweeps() in front of its call's last kKeepSweeps -- interior cost-to-go slots unwritten for the problems that run on
+    void launch_bp(hipStream_t s, int store_candidates, bool fused_hook = false, bool lean = false) {
         const unsigned B = cfg.batch;
         switch (plan.bp) {
         case kBpMfma:
@@ -386,8 +401,8 @@ struct Solver : SolverBase {
                 // the nominal-state / control weights + the compact position block b.Hc
                 const bool ee = cfg.ee_cost != 0;
                 const bool diag_h = !h_overridden && (!ee || b.Hc != nullptr);
-                launch_bp_mfma<T>(s, b, dm, (int)B, diag_h, hw[0], hw[1], hw[2], dt, keep_all_ctg() || store_candidates,
-                                  plan.sweep_fused && (!store_candidates || fused_hook), ee ? 1 : 0);      // (per-problem weights: the diagonal comes from the table, not from hw)
+                launch_bp_mfma<T>(s, b, dm, (int)B, diag_h, hw[0], hw[1], hw[2], dt, (keep_all_ctg() && !lean) || store_candidates,
+                                  plan.sweep_fused && (!store_candidates || fused_hook), ee ? 1 : 0, lean ? &sp : nullptr);      // (per-problem weights: the diagonal comes from the table, not from hw)
             }
             break;
         case kBpLg:
@@ -421,10 +436,10 @@ struct Solver : SolverBase {
         case kBpCoop: hipLaunchKernelGGL((k_bp<P, T>), dim3(cfg.M, B), dim3(64), 0, s, b, dm); break;
         }
     }
-    // one sweep, or its phase `only`.  store_candidates: the phase hook; part 0 / 1: the forward pass's sweep / rollout kernel alone (per-kernel timing)
-    void launch_sweep(hipStream_t s, int only = -1, int store_candidates = 0, int part = -1) {
+    // one sweep, or its phase `only`.  store_candidates: the phase hook; part 0 / 1: the forward pass's sweep / rollout kernel alone (per-kernel timing); lean: launch_bp
+    void launch_sweep(hipStream_t s, int only = -1, int store_candidates = 0, int part = -1, bool lean = false) {
         const unsigned B = cfg.batch;
-        if (only < 0 || only == PDDP_PHASE_BP) launch_bp(s, store_candidates);
+        if (only < 0 || only == PDDP_PHASE_BP) launch_bp(s, store_candidates, false, lean);
         if (only < 0 || only == PDDP_PHASE_FP) launch_fp(s, store_candidates ? kFpHook : part == 0 ? kFpSweepOnly : part == 1 ? kFpRolloutsOnly : kFpProduction);
         if ((only < 0 || only == PDDP_PHASE_LS) && !(plan.ls_in_rollouts && !store_candidates)) {      // (k_fp_tl4 ended with the line search of its problems)
             if (plan.ls_many) hipLaunchKernelGGL((k_ls_many<T>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, b, dm, sp, bench_mode, (int)B);
@@ -444,8 +459,9 @@ struct Solver : SolverBase {
         note_sweeps_enqueued();
         if (int erc = need_events(7 * (size_t)sweeps)) return erc;
         for (int i = 0; i < sweeps; i++) {
+            const bool lean = split_sweeps() && i + kKeepSweeps < sweeps;                         // (pddp_iterate's schedule)
             HIPCHK(hipEventRecord(trace_ev[7 * i], stream));
-            for (int k = 0; k < 6; k++) { if (nm[k][0]) launch_sweep(stream, phase_of[k], 0, part_of[k]); HIPCHK(hipEventRecord(trace_ev[7 * i + k + 1], stream)); }
+            for (int k = 0; k < 6; k++) { if (nm[k][0]) launch_sweep(stream, phase_of[k], 0, part_of[k], lean); HIPCHK(hipEventRecord(trace_ev[7 * i + k + 1], stream)); }
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
@@ -459,12 +475,15 @@ struct Solver : SolverBase {
     }
     // One sweep is one graph; a second executable holds kGraphUnroll sweeps back to back: between the kernels INSIDE a graph there is no gap, between two graph
     // launches ~9 us (measured, rocprofv3 kernel trace) -- 5 % of a single problem's 175 us iteration, nothing at large batch.
+    // With split_sweeps() each exists twice: graph / graph_n end a call (graph: one keeping sweep; graph_n: kGraphUnroll - kKeepSweeps lean sweeps and the
+    // kKeepSweeps keeping ones), graph_lean / graph_n_lean hold lean sweeps only.
     static constexpr int kGraphUnroll = 4;
-    hipGraphExec_t graph_n = nullptr;
-    int capture_sweeps(int count, hipGraphExec_t* out) {
+    hipGraphExec_t graph_n = nullptr, graph_n_lean = nullptr;
+    // `count` sweeps, the first `lean` of them lean
+    int capture_sweeps(int count, int lean, hipGraphExec_t* out) {
         hipGraph_t gr;
         HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        for (int i = 0; i < count; i++) launch_sweep(stream);
+        for (int i = 0; i < count; i++) launch_sweep(stream, -1, 0, -1, i < lean);
         {   // a failed launch inside the capture must not leave the stream capturing
             const hipError_t le = hipGetLastError(), ce = hipStreamEndCapture(stream, &gr);
             if (le != hipSuccess || ce != hipSuccess) {
@@ -484,22 +503,33 @@ struct Solver : SolverBase {
     int iterate(int sweeps) override {
         if (plan.bp_mfma && !keep_all_ctg()) lean_ctg_ran = true;
         if (sweeps > 0) note_sweeps_enqueued();
-        if (cfg.use_graph) {
-            if (!graph || graph_mode != bench_mode + 2 * sp.max_iter) {
-                if (graph) { hipGraphExecDestroy(graph); graph = nullptr; }
-                if (graph_n) { hipGraphExecDestroy(graph_n); graph_n = nullptr; }
-                int rc = capture_sweeps(1, &graph);
+        const bool split = split_sweeps();                                             // every sweep but the last kKeepSweeps is lean
+        if (sweeps > 0 && cfg.use_graph) {
+            const int key = bench_mode + 2 * sp.max_iter + (split ? 1 << 30 : 0);      // (the iteration limit is part of a lean pass's arguments; graph_n holds lean sweeps only with the split)
+            if (!graph || graph_mode != key) {
+                drop_graph();
+                int rc = capture_sweeps(1, 0, &graph);
                 if (rc) return rc;
-                graph_mode = bench_mode + 2 * sp.max_iter;
+                graph_mode = key;
             }
-            int left = sweeps;
-            if (left >= kGraphUnroll && (size_t)cfg.batch * cfg.N <= 65536) {          // only where a launch gap is a visible share of a sweep
-                if (!graph_n) { int rc = capture_sweeps(kGraphUnroll, &graph_n); if (rc) return rc; }
-                for (; left >= kGraphUnroll; left -= kGraphUnroll) HIPCHK(hipGraphLaunch(graph_n, stream));
+            // executables captured on first use; without the split the keeping ones stand for both kinds
+            auto need = [&](hipGraphExec_t* g, int count, int lean) { return *g ? 0 : capture_sweeps(count, lean, g); };
+            const bool unroll = sweeps >= kGraphUnroll && (size_t)cfg.batch * cfg.N <= 65536;      // only where a launch gap is a visible share of a sweep
+            const int tail = unroll ? kGraphUnroll : sweeps < kKeepSweeps ? sweeps : kKeepSweeps;      // sweeps of the executable(s) that end the call
+            int front = sweeps - tail;
+            if (split && front > 0) { if (int rc = need(&graph_lean, 1, 1)) return rc; }
+            hipGraphExec_t one = split ? graph_lean : graph;
+            if (unroll) {
+                if (int rc = need(&graph_n, kGraphUnroll, split ? kGraphUnroll - kKeepSweeps : 0)) return rc;
+                if (split && front >= kGraphUnroll) { if (int rc = need(&graph_n_lean, kGraphUnroll, kGraphUnroll)) return rc; }
+                hipGraphExec_t four = split ? graph_n_lean : graph_n;
+                for (; front >= kGraphUnroll; front -= kGraphUnroll) HIPCHK(hipGraphLaunch(four, stream));
             }
-            for (int i = 0; i < left; i++) HIPCHK(hipGraphLaunch(graph, stream));
+            for (; front > 0; front--) HIPCHK(hipGraphLaunch(one, stream));
+            if (unroll) HIPCHK(hipGraphLaunch(graph_n, stream));
+            else for (int i = 0; i < tail; i++) HIPCHK(hipGraphLaunch(graph, stream));
         } else {
-            for (int i = 0; i < sweeps; i++) launch_sweep(stream);
+            for (int i = 0; i < sweeps; i++) launch_sweep(stream, -1, 0, -1, split && i + kKeepSweeps < sweeps);
         }
         HIPCHK(hipGetLastError());
         return 0;
@@ -516,8 +546,9 @@ struct Solver : SolverBase {
         const bool own_sweep = !plan.maps_in_rollouts;                                  // (otherwise the rollout kernel begins with it: row 4 stays 0)
         const int part_of[5] = {-1, 0, own_sweep ? 1 : -1, -1, -1};
         for (int i = 0; i < sweeps; i++) {
+            const bool lean = split_sweeps() && i + kKeepSweeps < sweeps;                   // (pddp_iterate's schedule)
             HIPCHK(hipEventRecord(trace_ev[6 * i], stream));
-            for (int k = 0; k < 5; k++) { if (k != 1 || own_sweep) launch_sweep(stream, phase_of[k], 0, part_of[k]); HIPCHK(hipEventRecord(trace_ev[6 * i + k + 1], stream)); }
+            for (int k = 0; k < 5; k++) { if (k != 1 || own_sweep) launch_sweep(stream, phase_of[k], 0, part_of[k], lean); HIPCHK(hipEventRecord(trace_ev[6 * i + k + 1], stream)); }
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));

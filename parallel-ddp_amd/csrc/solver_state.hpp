@@ -147,4 +147,20 @@ PDDP_HD void line_search_accept(SolverState<T>& st, const SolverParams& sp, cons
     if (st.iter == sp.max_iter) st.done = 2; else { st.iter += 1; st.pw ^= 1; }   // Pp <- P, pp <- p of nextIterationSetupGPU (:266-267), by index
 }
 
+// Can the line search of THIS sweep or of the NEXT end the problem?  The matrix-core backward pass asks before it leaves the interior cost-to-go of a problem unwritten
+// (bp_mfma.hpp kMxLeanIfRunning): a caller can read the interiors of a problem's last two passes, so neither of them may be a lean one.  `flags` are the pass's: bit 3
+// (kMxMaxRhoExit) = the handle exits at the maximum rho (!ignore_max_rho_exit), the call's iteration limit from bit kMxMaxIterShift up (lean_flags_max_iter: clamped, and
+// a smaller limit only keeps more).  The caller has ruled out the exit by tolerance (tol_cost <= 0 with a cost that is never negative: an accepted step's relative
+// decrease dJ / prevJ is then never below it).  max_iter: `iter` advances by at most one per sweep and the exit is taken at iter == max_iter.  Maximum rho: taken at a
+// rejection that leaves rho at kRhoMax, and no two outcomes raise rho further than two rejections do.  The third way to done = 3, a failed inversion, needs a pass that
+// reports failures: not this rule's.
+constexpr int kMxLeanIfRunning = 4, kMxMaxRhoExit = 8, kMxMaxIterShift = 8;
+PDDP_HD constexpr int lean_flags_max_iter(int max_iter) { return (max_iter < (1 << 22) ? max_iter : (1 << 22) - 1) << kMxMaxIterShift; }
+template <typename T>
+PDDP_HD bool may_exit_within_two(const SolverState<T>& st, int flags) {
+    if (st.iter >= (flags >> kMxMaxIterShift) - 1) return true;
+    if (flags & kMxMaxRhoExit) { SolverState<T> t = st; rho_increase(t); rho_increase(t); if (t.rho == T(kRhoMax)) return true; }
+    return false;
+}
+
 }  // namespace pddp
