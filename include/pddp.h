@@ -287,7 +287,8 @@ int pddp_get_diag_cost_problems(pddp_handle h, int count, const int* idx, double
  * never calls the setter launches exactly the kernels and arguments it launches without these entry points.
  * Control cycles (pddp_mpc_solve, pddp_mpc_solve_problems, pddp_mpc_load*): the library does NOT shift a goal trajectory.  The rows are
  * the goals of the NEW horizon's knots 0..N-1 as they stand when the cycle starts; a caller that tracks a moving window writes the new
- * window with the setter before the cycle (count * N * n numbers of upload).  pddp_load_problems / pddp_mpc_solve_problems /
+ * window with the setter before the cycle (count * N * n numbers of upload) -- or gives the problem a goal PATH (below), whose window
+ * the library moves itself.  pddp_load_problems / pddp_mpc_solve_problems /
  * pddp_mpc_load_problems run the named slots with their own trajectories; a cycle does not change a trajectory.
  * pddp_get_goal_trajectory_problems returns the stored rows and has[i] = 1 for a problem with a trajectory; for a problem without one
  * (and for every problem before the first setter call) that problem's xGoal repeated N times and has[i] = 0.  has may be NULL.
@@ -299,6 +300,56 @@ int pddp_goal_trajectory_size(pddp_handle h);                                   
 int pddp_set_goal_trajectory_problems(pddp_handle h, int count, const int* idx, const void* G /* [count][N][n], handle dtype */);
 int pddp_get_goal_trajectory_problems(pddp_handle h, int count, const int* idx, void* G /* [count][N][n] */, int* has /* [count], may be NULL */);
 int pddp_clear_goal_trajectory_problems(pddp_handle h, int count, const int* idx);
+/* Goal paths of the same plants: a device-resident reference per problem, windowed by every control cycle.  Where a tracking caller would
+ * write the horizon's window with pddp_set_goal_trajectory_problems before each cycle (count * N * n numbers of upload), it uploads the
+ * whole reference once.  A problem of plants 1-3 has no trajectory, a goal trajectory G[N][n] (above), or a goal PATH: the device holds
+ * path[len][n] in the handle's element type (1 <= len <= capacity), a mode and a cursor in [0, len).  The goal of horizon knot k is
+ * path[row(cursor, k)]:
+ *   PDDP_GOAL_PATH_HOLD  row = min(cursor + k, len - 1): the last row is held
+ *   PDDP_GOAL_PATH_WRAP  row = (cursor + k) % len, a true modulo: len may be smaller than N, the window then laps the path
+ * Advancing by s knots: HOLD cursor = min(cursor + s, len - 1), WRAP cursor = (cursor + s) % len.  The cursor is stored in this canonical
+ * form.
+ * THE INVARIANT: for a problem with a path, its block of the goal table [batch][N][n] (the table of the goal trajectories, flag 1) always
+ * holds the window at its cursor.  Every kernel that reads a goal is therefore unchanged, and pddp_load, pddp_load_problems, pddp_solve,
+ * the named-slot calls, the captured graph and pddp_get_goal_trajectory_problems (which returns the window with has = 1) behave as they do
+ * for a plain trajectory holding those rows.  Only the calls below move a cursor and rewrite a window.
+ * WHO ADVANCES THE CURSOR: every call that shifts the previous solution.  pddp_mpc_solve and pddp_mpc_load advance every problem with a
+ * path by shift[b]; pddp_mpc_solve_problems and pddp_mpc_load_problems advance the named slots that have a path by their entry of shift,
+ * and the slots that are not named keep cursor and rows bit for bit.  The advance happens whatever clear_vars and full_rollout are; it
+ * stays in force when the solve falls back (success = 0: the fall-back solution is the shifted one); it happens only after the call's
+ * argument checks have passed (a refused call leaves cursors and rows unchanged); pddp_mpc_load followed by pddp_mpc_solve advances twice,
+ * exactly as the solution is shifted twice.  The window is written on the device by one mover kernel in front of the cycle (two passes
+ * over count * N * n numbers of device memory, no upload).  Nothing else moves a cursor: not pddp_load*, pddp_solve or pddp_iterate.
+ * pddp_reserve_goal_path: room for `capacity` rows per problem and a record {len, mode, cursor} per problem (len = 0: no path); creates
+ * the goal table and the table of diagonal cost records the way the first pddp_set_goal_trajectory_problems call does and drops the
+ * captured sweep graph once, there and in no other call of this group.  The same capacity again is a successful no-op; another capacity,
+ * capacity < 1 or a capacity for which capacity + N does not fit an int is PDDP_EINVAL; a failed allocation is PDDP_ENOMEM with the
+ * handle unchanged.  pddp_goal_path_capacity: the capacity, 0 before the reserve.
+ * pddp_set_goal_path_problems: uploads path[count][len][n], writes the records (cursor NULL: every cursor 0), flags the problems and
+ * writes their windows, on the solver's stream with one synchronisation before it returns.  Timing is that of the trajectory setter:
+ * H, g and the cost of what is already in a slot are not rebuilt; problems that are not named keep theirs.
+ * pddp_set_goal_path_cursor_problems: moves the cursors of problems that have a path and rewrites their windows.
+ * pddp_get_goal_path_problems: len, mode and the canonical cursor per problem (0, 0, 0 without a path) and, where path is not NULL, the
+ * rows as [count][capacity][n] with every row >= len zero.  len, mode, cursor and path may each be NULL.
+ * pddp_set_goal_trajectory_problems on a problem that has a path turns it into a plain trajectory (len = 0);
+ * pddp_clear_goal_trajectory_problems removes a path with its window.  Neither behaves differently on a handle without a reserve, and a
+ * handle without a path launches exactly what it launches without these entry points.
+ * PDDP_EINVAL, with the handle unchanged: plants 4 and 5; no reserve; count < 1; a NULL idx or path (setter) or cursor (cursor call); an
+ * index outside [0, batch) or named twice; len outside [1, capacity]; a mode other than 1 or 2; a cursor outside [0, len); a value that
+ * is not finite in the handle's element type; (cursor call) a named problem without a path.  The handle need not be loaded. */
+#define PDDP_GOAL_PATH_HOLD 1
+#define PDDP_GOAL_PATH_WRAP 2
+int pddp_reserve_goal_path(pddp_handle h, int capacity);   /* rows per problem */
+int pddp_goal_path_capacity(pddp_handle h);                /* 0 before the reserve */
+int pddp_set_goal_path_problems(pddp_handle h, int count, const int* idx, int len, int mode,
+                                const int* cursor /* [count], NULL = 0 */, const void* path /* [count][len][n], handle dtype */);
+int pddp_set_goal_path_cursor_problems(pddp_handle h, int count, const int* idx, const int* cursor);
+int pddp_get_goal_path_problems(pddp_handle h, int count, const int* idx, int* len, int* mode, int* cursor,
+                                void* path /* [count][capacity][n], may be NULL; rows >= len are zero */);
+/* Measurement hook (tools/goal_path_time.py, profiles/goal_path.md), like pddp_mpc_slots_profile: timing = 1 / 0: record HIP events around the
+ * mover kernel in front of the following control cycles / stop (-1: keep); it changes nothing of what the calls compute or launch.  ms, when not
+ * NULL, receives the last timed launch's stream time in ms (0 when none was timed). */
+int pddp_goal_path_profile(pddp_handle h, int timing, float* ms);
 /* ---- the lock-step experiment around the solver ------------------------- */
 /* simulateForward<T, SUBSTEPS> (examples/WAFR_MPC_examples.cu:111-139): the simulated robot of the lock-step MPC experiment.  Starting
  * from xActual at plant time t0_us (the plan's t0), integrates the plant IN DOUBLE for elapsed_us in `substeps` steps under the trajectory

@@ -12,6 +12,7 @@
 #include "bp_cl.hpp"
 #include "bp_mq.hpp"
 #include "kernel_plan.hpp"
+#include "goal_path_table.hpp"
 #include "mpc.hpp"
 #include "mpc_record.hpp"
 #include "sim.hpp"
@@ -1051,6 +1052,46 @@ __global__ __launch_bounds__(256) void k_mpc_store(Buffers<T> b, MpcBuffers<T> m
     const T* us = old ? mb.u_old + (size_t)pb * N * NU : b.ucur + (size_t)pb * N * NU;
     const T* ks = old ? mb.KT_old + (size_t)pb * N * NX * NU : b.KT + (size_t)pb * N * NX * NU;
     mpc_record_pack<T>(rec, r, threadIdx.x, blockDim.x, xs, us, ks, b.Jout + (size_t)pb * rec.out_stride, b.alphaOut + (size_t)pb * rec.out_stride);
+}
+
+// The window of a goal path (goal_path_table.hpp), in front of a control cycle: grid (count), block 256.  Entry i serves problem idx[i] (idx null: problem i): its
+// cursor moves on by shift[i] knots (shift null: it stays) and the N rows path[row(cursor, k)] go into the problem's block of the goal table, which is all the sweep
+// kernels ever read (GoalTab, plants.hpp).  A problem without a path (len = 0) is left alone.  ONE workgroup per problem: every thread reads the record and derives
+// the new cursor from it, and only behind the barrier does thread 0 write the cursor back -- no thread of the block can read an advanced cursor, no other block reads
+// this record at all.  A pure mover: threads run over (knot, chunk) pairs with the widest access the row size allows (16 bytes; 8 for the float pendulum's rows), so
+// consecutive lanes write consecutive addresses of the table; the rows of a knot are contiguous on both sides.  path and gtab are separate blocks.
+template <int W> struct GoalChunk;
+template <> struct GoalChunk<16> { using type = uint4; };
+template <> struct GoalChunk<8> { using type = uint2; };
+template <> struct GoalChunk<4> { using type = unsigned; };
+template <int W>
+__device__ __forceinline__ void goal_window_rows(unsigned char* dst, const unsigned char* src, const GoalPathRec r, int N, unsigned row_bytes) {
+    using V = typename GoalChunk<W>::type;
+    const unsigned per = row_bytes / W, total = (unsigned)N * per;
+    for (unsigned t = threadIdx.x; t < total; t += blockDim.x) {
+        const unsigned k = t / per, c = t - k * per;
+        const size_t from = (size_t)goal_path_row(r.cursor, (int)k, r.len, r.mode) * row_bytes + (size_t)c * W;
+        *reinterpret_cast<V*>(dst + (size_t)t * W) = *reinterpret_cast<const V*>(src + from);
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_goal_window(const T* __restrict__ path, GoalPathRec* meta, T* __restrict__ gtab, const int* __restrict__ idx, const int* __restrict__ shift,
+                                                     int count, int batch, int N, int NX, int capacity) {
+    const int i = blockIdx.x;
+    if (i >= count) return;
+    const int q = idx ? idx[i] : i;
+    if (q < 0 || q >= batch) return;                               // (uniform per block, before the barrier; validated on the host: a stale index must not become a stray write)
+    GoalPathRec r = meta[q];
+    if (r.len <= 0) return;                                        // no path (uniform per block)
+    r.cursor = goal_path_advance(r.cursor, shift ? shift[i] : 0, r.len, r.mode);
+    __syncthreads();                                               // every thread has read the old cursor
+    if (threadIdx.x == 0) meta[q].cursor = r.cursor;
+    const unsigned row_bytes = (unsigned)NX * (unsigned)sizeof(T);
+    unsigned char* dst = reinterpret_cast<unsigned char*>(gtab + (size_t)q * N * NX);
+    const unsigned char* src = reinterpret_cast<const unsigned char*>(path + (size_t)q * capacity * NX);
+    if (row_bytes % 16 == 0) goal_window_rows<16>(dst, src, r, N, row_bytes);
+    else if (row_bytes % 8 == 0) goal_window_rows<8>(dst, src, r, N, row_bytes);
+    else goal_window_rows<4>(dst, src, r, N, row_bytes);
 }
 
 // initial cost + solver state: grid (B), block 64, dynamic LDS N*sizeof(T).

@@ -140,6 +140,17 @@ extern "C" int pddp_goal_trajectory_size(pddp_handle h) {
 extern "C" int pddp_set_goal_trajectory_problems(pddp_handle h, int count, const int* idx, const void* G) { IMPL(h); return s->set_goal_trajectory_problems(count, idx, G); }
 extern "C" int pddp_get_goal_trajectory_problems(pddp_handle h, int count, const int* idx, void* G, int* has) { IMPL(h); return s->get_goal_trajectory_problems(count, idx, G, has); }
 extern "C" int pddp_clear_goal_trajectory_problems(pddp_handle h, int count, const int* idx) { IMPL(h); return s->clear_goal_trajectory_problems(count, idx); }
+// goal paths of the same plants (goal_path_table.hpp): the handle checks every argument before it is touched
+extern "C" int pddp_reserve_goal_path(pddp_handle h, int capacity) { IMPL(h); return s->reserve_goal_path(capacity); }
+extern "C" int pddp_goal_path_capacity(pddp_handle h) { IMPL(h); return s->goal_path_capacity(); }
+extern "C" int pddp_set_goal_path_problems(pddp_handle h, int count, const int* idx, int len, int mode, const int* cursor, const void* path) {
+    IMPL(h); return s->set_goal_path_problems(count, idx, len, mode, cursor, path);
+}
+extern "C" int pddp_set_goal_path_cursor_problems(pddp_handle h, int count, const int* idx, const int* cursor) { IMPL(h); return s->set_goal_path_cursor_problems(count, idx, cursor); }
+extern "C" int pddp_get_goal_path_problems(pddp_handle h, int count, const int* idx, int* len, int* mode, int* cursor, void* path) {
+    IMPL(h); return s->get_goal_path_problems(count, idx, len, mode, cursor, path);
+}
+extern "C" int pddp_goal_path_profile(pddp_handle h, int timing, float* ms) { IMPL(h); return s->goal_path_profile(timing, ms); }
 extern "C" int pddp_simulate(pddp_handle h, const void* x, const void* u, const void* KT, double t0_us, double elapsed_us, int substeps, const void* goal_xyz,
                              void* xActual_inout, double* avg_err, int* failed) {
     IMPL(h); if (!x || !u || !KT || !xActual_inout) return fail(PDDP_EINVAL, "null argument");

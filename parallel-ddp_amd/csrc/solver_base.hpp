@@ -84,6 +84,13 @@ struct SolverBase {
     virtual int set_goal_trajectory_problems(int count, const int* idx, const void* G) = 0;
     virtual int get_goal_trajectory_problems(int count, const int* idx, void* G, int* has) = 0;
     virtual int clear_goal_trajectory_problems(int count, const int* idx) = 0;
+    // goal paths of the same plants (goal_path_table.hpp): device-resident references, windowed into the goal table by every call that shifts the previous solution
+    virtual int reserve_goal_path(int capacity) = 0;
+    virtual int goal_path_capacity() = 0;          // rows per problem; 0 before the reserve
+    virtual int set_goal_path_problems(int count, const int* idx, int len, int mode, const int* cursor, const void* path) = 0;
+    virtual int set_goal_path_cursor_problems(int count, const int* idx, const int* cursor) = 0;
+    virtual int get_goal_path_problems(int count, const int* idx, int* len, int* mode, int* cursor, void* path) = 0;
+    virtual int goal_path_profile(int on, float* ms) = 0;       // pddp_goal_path_profile (measurement)
     virtual int mpc_solve(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout, int ifd, int max_iter, double budget_ms,
                           int poll_every, void* x, void* u, void* KT, void* Jout, int* alphaOut, int* success, int* iters) = 0;
     virtual int mpc_load(const void* xActual, const void* xGoal, const int* shift, int clear_vars, int full_rollout) = 0;   // mpc_solve's load stage alone (teacher-forcing hook)

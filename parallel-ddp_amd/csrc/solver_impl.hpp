@@ -8,6 +8,7 @@
 #include "cost_table.hpp"
 #include "diag_cost_table.hpp"
 #include "goal_traj_table.hpp"
+#include "goal_path_table.hpp"
 #include "mpc_slots.hpp"
 #include "mpc_record.hpp"
 #include "tl_launch.hpp"
@@ -129,6 +130,7 @@ struct Solver : SolverBase {
         drop_graph();
         for (hipEvent_t e : trace_ev) hipEventDestroy(e);
         for (hipEvent_t e : slots_ev) if (e) hipEventDestroy(e);
+        for (hipEvent_t e : gp_ev) if (e) hipEventDestroy(e);
         delete intake;                                              // (before the stream it runs on)
         if (stream && !intake_of) hipStreamDestroy(stream);        // (an intake area runs on its handle's stream)
     }
@@ -754,6 +756,7 @@ struct Solver : SolverBase {
         const std::string complaint = goal_rows_complaint<T>(count, idx, G, cfg.batch, cfg.N, NX);
         if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_goal_trajectory_problems: " + complaint);
         if (int rc = ensure_goal_table()) return rc;
+        if (int rc = goal_path_drop(count, idx)) return rc;         // (a named problem with a goal path becomes one with a plain trajectory)
         const size_t len = goal_len();
         hipError_t e = hipSuccess;
         for_each_slot_run(count, idx, [&](int first, int run) {     // contiguous runs of slots in one transfer each; problems that are not named keep theirs
@@ -769,6 +772,7 @@ struct Solver : SolverBase {
         const std::string complaint = goal_rows_complaint<T>(count, idx, nullptr, cfg.batch, cfg.N, NX, false);
         if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_clear_goal_trajectory_problems: " + complaint);
         if (!b.gtab) return 0;                                      // never had a trajectory: every problem reads xGoal already
+        if (int rc = goal_path_drop(count, idx)) return rc;         // (a goal path goes with its window)
         const int rc = goal_flags_upload(count, idx, 0);
         HIPCHK(hipStreamSynchronize(stream));
         return rc;
@@ -794,6 +798,155 @@ struct Solver : SolverBase {
         for (int i = 0; i < count; i++) {
             if (!gf_stage[i]) goal_rows_from_xgoal<T>(gt_stage.data() + (size_t)i * NX, cfg.N, NX, G + (size_t)i * len);      // no trajectory: what the cost reads, xGoal at every knot
             if (has) has[i] = gf_stage[i] ? 1 : 0;
+        }
+        return 0;
+    }
+    // ---- goal paths of the same plants (goal_path_table.hpp, k_goal_window in kernels.hpp): pddp_reserve_goal_path / pddp_set_goal_path_problems / ..._cursor_problems / pddp_get_...
+    // path[batch][capacity][NX] and a record {len, mode, cursor} per problem on the device, from the reserve on.  The invariant: the block of the goal table of a
+    // problem with a path holds the window at its cursor, so nothing that reads a goal knows about paths.  k_goal_window restores it wherever a cursor moves: in the
+    // setter and the cursor call, and in front of every load stage of a control cycle (mpc_launch_load for the whole handle, mpc_problems for named slots), by the
+    // call's shifts.  The host keeps len and mode of every problem (gp_host; the cursor lives on the device alone) and the number of problems with a path: no launch
+    // and no transfer is added to a call of a handle where that number is zero.
+    DeviceBuf d_gpath, d_gpmeta, d_gp_idx, d_gp_shift;
+    int gp_capacity = 0;                           // rows per problem; 0: no reserve
+    int gp_count = 0;                              // problems with a path
+    std::vector<GoalPathRec> gp_host;              // [batch] len and mode as last written (cursor unused)
+    std::vector<GoalPathRec> gp_stage;             // host records of the call in flight
+    T* gpath_rows() const { return d_gpath.template as<T>(); }
+    GoalPathRec* gpmeta_rows() const { return d_gpmeta.template as<GoalPathRec>(); }
+    int reserve_goal_path(int capacity) override {
+        if (!kDiagCost) return goal_refuse("pddp_reserve_goal_path");
+        const std::string complaint = goal_path_reserve_complaint(capacity, cfg.N, gp_capacity);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_reserve_goal_path: " + complaint);
+        if (gp_capacity) return 0;                                  // the same capacity again
+        const size_t B = cfg.batch, per = (size_t)NX * sizeof(T);
+        if ((size_t)capacity > ((size_t)-1) / (B * per)) return fail(PDDP_ENOMEM, "pddp_reserve_goal_path: batch * capacity * n elements do not fit the address space");
+        const size_t bytes = B * (size_t)capacity * per;
+        int rc = reserve(d_gpath, bytes, "hipMalloc failed for the goal paths");
+        if (!rc) rc = reserve(d_gpmeta, B * sizeof(GoalPathRec), "hipMalloc failed for the goal paths' records");
+        if (!rc) rc = reserve(d_gp_idx, B * sizeof(int), "hipMalloc failed for the goal paths' index list");
+        if (!rc) rc = reserve(d_gp_shift, kSlotIntakeMax * sizeof(int), "hipMalloc failed for the goal paths' chunk shifts");
+        if (!rc && (hipMemsetAsync(d_gpath.ptr, 0, bytes, stream) != hipSuccess || hipMemsetAsync(d_gpmeta.ptr, 0, B * sizeof(GoalPathRec), stream) != hipSuccess))
+            rc = fail(PDDP_ENODEVICE, "pddp_reserve_goal_path: clearing the goal paths failed");
+        if (!rc) rc = ensure_goal_table();                          // (the goal table and the cost table as by the first trajectory setter call: waits for the stream, drops the graph once)
+        if (rc) { hipStreamSynchronize(stream); d_gpath.release(); d_gpmeta.release(); d_gp_idx.release(); d_gp_shift.release(); return rc; }
+        HIPCHK(hipStreamSynchronize(stream));
+        gp_host.assign(B, GoalPathRec{0, 0, 0});
+        gp_count = 0; gp_capacity = capacity;
+        return 0;
+    }
+    int goal_path_capacity() override { return kDiagCost ? gp_capacity : goal_refuse("pddp_goal_path_capacity"); }
+    // gp_stage[first .. first + run) -> the records of slots idx[first] ..., one transfer per run of ascending slots
+    hipError_t goal_path_records_upload(int count, const int* idx) {
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int run) {
+            if (e == hipSuccess) e = hipMemcpyAsync(gpmeta_rows() + idx[first], gp_stage.data() + first, (size_t)run * sizeof(GoalPathRec), hipMemcpyHostToDevice, stream);
+        });
+        return e;
+    }
+    // the windows of the named problems at their cursors, enqueued (setter and cursor call: no shift)
+    hipError_t goal_path_window_named(int count, const int* idx) {
+        const hipError_t e = hipMemcpyAsync(d_gp_idx.ptr, idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_goal_window<T>), dim3(count), dim3(256), 0, stream, (const T*)gpath_rows(), gpmeta_rows(), gtab_rows(), (const int*)d_gp_idx.template as<int>(),
+                           (const int*)nullptr, count, (int)cfg.batch, (int)cfg.N, (int)NX, gp_capacity);
+        return hipGetLastError();
+    }
+    // the windows of entries [0, n) moved on by their shifts, in front of a load stage: d_idx null: problem i, else slot d_idx[i]; d_sh: the shifts on the device
+    void goal_path_advance_enqueue(int n, const int* d_idx, const int* d_sh) {
+        if (gp_timing) hipEventRecord(gp_ev[0], stream);
+        hipLaunchKernelGGL((k_goal_window<T>), dim3(n), dim3(256), 0, stream, (const T*)gpath_rows(), gpmeta_rows(), gtab_rows(), d_idx, d_sh, n, (int)cfg.batch, (int)cfg.N, (int)NX,
+                           gp_capacity);
+        if (gp_timing) { hipEventRecord(gp_ev[1], stream); gp_timed = true; }
+    }
+    // pddp_goal_path_profile (measurement): HIP events around the k_goal_window launch in front of a control cycle; ms: the last timed launch's stream time
+    bool gp_timing = false, gp_timed = false;
+    hipEvent_t gp_ev[2] = {nullptr, nullptr};
+    int goal_path_profile(int on, float* ms) override {
+        if (on >= 0) {
+            if (on && !gp_ev[0]) for (hipEvent_t& e : gp_ev) HIPCHK(hipEventCreate(&e));
+            gp_timing = on != 0;
+        }
+        if (ms) {
+            *ms = 0.f;
+            if (gp_timed) { HIPCHK(hipEventSynchronize(gp_ev[1])); HIPCHK(hipEventElapsedTime(ms, gp_ev[0], gp_ev[1])); }
+        }
+        return 0;
+    }
+    // the named problems that have a path lose it (their block of the goal table stays what it is): enqueued; nothing at all on a handle without paths
+    int goal_path_drop(int count, const int* idx) {
+        if (!gp_count) return 0;
+        bool any = false;
+        for (int i = 0; i < count; i++) any |= gp_host[idx[i]].len != 0;
+        if (!any) return 0;
+        gp_stage.assign((size_t)count, GoalPathRec{0, 0, 0});
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < count && e == hipSuccess; i++)          // (only the records of problems that had a path are written)
+            if (gp_host[idx[i]].len) e = hipMemcpyAsync(gpmeta_rows() + idx[i], gp_stage.data() + i, sizeof(GoalPathRec), hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) { hipStreamSynchronize(stream); return fail(PDDP_ENODEVICE, std::string("goal paths: transfer of records failed: ") + hipGetErrorString(e)); }
+        for (int i = 0; i < count; i++) if (gp_host[idx[i]].len) { gp_host[idx[i]] = GoalPathRec{0, 0, 0}; gp_count--; }
+        return 0;
+    }
+    int set_goal_path_problems(int count, const int* idx, int len, int mode, const int* cursor, const void* pv) override {
+        if (!kDiagCost) return goal_refuse("pddp_set_goal_path_problems");
+        if (!gp_capacity) return fail(PDDP_EINVAL, "pddp_set_goal_path_problems: the handle has no goal path storage (pddp_reserve_goal_path)");
+        const T* path = static_cast<const T*>(pv);
+        const std::string complaint = goal_path_set_complaint<T>(count, idx, len, mode, cursor, path, cfg.batch, gp_capacity, NX);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_goal_path_problems: " + complaint);
+        const size_t per = (size_t)len * NX, slot = (size_t)gp_capacity * NX;
+        hipError_t e = hipSuccess;
+        if (len == gp_capacity) {                                   // full blocks: runs of ascending slots are contiguous on both sides
+            for_each_slot_run(count, idx, [&](int first, int run) {
+                if (e == hipSuccess) e = hipMemcpyAsync(gpath_rows() + (size_t)idx[first] * slot, path + (size_t)first * per, (size_t)run * per * sizeof(T), hipMemcpyHostToDevice, stream);
+            });
+        } else {
+            for (int i = 0; i < count && e == hipSuccess; i++)
+                e = hipMemcpyAsync(gpath_rows() + (size_t)idx[i] * slot, path + (size_t)i * per, per * sizeof(T), hipMemcpyHostToDevice, stream);
+        }
+        gp_stage.resize((size_t)count);
+        for (int i = 0; i < count; i++) gp_stage[i] = GoalPathRec{len, mode, cursor ? cursor[i] : 0};
+        if (e == hipSuccess) e = goal_path_records_upload(count, idx);
+        if (e != hipSuccess) { hipStreamSynchronize(stream); return fail(PDDP_ENODEVICE, std::string("pddp_set_goal_path_problems: transfer failed: ") + hipGetErrorString(e)); }
+        int rc = goal_flags_upload(count, idx, 1);
+        if (!rc && (e = goal_path_window_named(count, idx)) != hipSuccess) rc = fail(PDDP_ENODEVICE, std::string("pddp_set_goal_path_problems: the window kernel failed: ") + hipGetErrorString(e));
+        for (int i = 0; i < count; i++) { if (!gp_host[idx[i]].len) gp_count++; gp_host[idx[i]] = GoalPathRec{len, mode, 0}; }      // (the records are on their way whatever follows)
+        HIPCHK(hipStreamSynchronize(stream));
+        return rc;
+    }
+    int set_goal_path_cursor_problems(int count, const int* idx, const int* cursor) override {
+        if (!kDiagCost) return goal_refuse("pddp_set_goal_path_cursor_problems");
+        if (!gp_capacity) return fail(PDDP_EINVAL, "pddp_set_goal_path_cursor_problems: the handle has no goal path storage (pddp_reserve_goal_path)");
+        const std::string complaint = goal_path_cursor_complaint(count, idx, cursor, gp_host.data(), cfg.batch);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_goal_path_cursor_problems: " + complaint);
+        gp_stage.resize((size_t)count);
+        for (int i = 0; i < count; i++) gp_stage[i] = GoalPathRec{gp_host[idx[i]].len, gp_host[idx[i]].mode, cursor[i]};
+        hipError_t e = goal_path_records_upload(count, idx);
+        if (e == hipSuccess) e = goal_path_window_named(count, idx);
+        const hipError_t es = hipStreamSynchronize(stream);
+        if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string("pddp_set_goal_path_cursor_problems: failed on the device: ") + hipGetErrorString(e != hipSuccess ? e : es));
+        return 0;
+    }
+    int get_goal_path_problems(int count, const int* idx, int* len, int* mode, int* cursor, void* pv) override {
+        if (!kDiagCost) return goal_refuse("pddp_get_goal_path_problems");
+        if (!gp_capacity) return fail(PDDP_EINVAL, "pddp_get_goal_path_problems: the handle has no goal path storage (pddp_reserve_goal_path)");
+        const std::string complaint = slots_complaint(count, idx, cfg.batch);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_get_goal_path_problems: " + complaint);
+        T* path = static_cast<T*>(pv);
+        const size_t slot = (size_t)gp_capacity * NX;
+        gp_stage.assign((size_t)count, GoalPathRec{0, 0, 0});
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int run) {
+            if (e == hipSuccess) e = hipMemcpyAsync(gp_stage.data() + first, gpmeta_rows() + idx[first], (size_t)run * sizeof(GoalPathRec), hipMemcpyDeviceToHost, stream);
+            if (path && e == hipSuccess) e = hipMemcpyAsync(path + (size_t)first * slot, gpath_rows() + (size_t)idx[first] * slot, (size_t)run * slot * sizeof(T), hipMemcpyDeviceToHost, stream);
+        });
+        const hipError_t es = hipStreamSynchronize(stream);
+        if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string("pddp_get_goal_path_problems: transfer failed: ") + hipGetErrorString(e != hipSuccess ? e : es));
+        for (int i = 0; i < count; i++) {
+            const GoalPathRec& r = gp_stage[i];
+            if (len) len[i] = r.len;
+            if (mode) mode[i] = r.mode;
+            if (cursor) cursor[i] = r.cursor;
+            if (path) for (size_t k = (size_t)r.len * NX; k < slot; k++) path[(size_t)i * slot + k] = T(0);      // rows >= len: what an earlier, longer path left there is not part of this one
         }
         return 0;
     }
@@ -838,6 +991,7 @@ struct Solver : SolverBase {
             HIPCHK(hipMemcpyAsync(d_goal_in, h + in.goal, in.x_bytes, hipMemcpyHostToDevice, stream));
             HIPCHK(hipMemcpyAsync(d_shift, h + in.shift, in.shift_bytes, hipMemcpyHostToDevice, stream));
         }
+        if (gp_count) goal_path_advance_enqueue((int)B, nullptr, d_shift);      // goal paths: cursors on by the shifts, the new windows in the goal table before anything reads a goal
         if constexpr (P::PLANT == 4 && INTEG == 1 && sizeof(T) == 4) {                // float arm with a built-in robot model: the warm-start rollout split over two waves
             if (plan.mpc_split_roll) {
                 if (tl_variant == 0) launch_mpc_load<0>(clear_vars, full_rollout, from, d_idx, from_batch);
@@ -1132,6 +1286,10 @@ struct Solver : SolverBase {
             in.cfg.batch = n;                                        // this chunk's view of the intake area, as in load_problems
             if (hipMemcpyAsync(slot_idx(), idx + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, std::string(who) + ": index transfer failed"); break; }
             if (slots_timing) hipEventRecord(slots_ev[0], stream);
+            if (gp_count) {                                          // goal paths: the chunk's slots are windowed in the HANDLE's table by the chunk's shifts, before the movers fetch blocks and flags
+                if (hipMemcpyAsync(d_gp_shift.ptr, shift + c0, n * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = fail(PDDP_ENODEVICE, std::string(who) + ": shift transfer failed"); break; }
+                goal_path_advance_enqueue(n, slot_idx(), d_gp_shift.template as<int>());
+            }
             for (const SlotTable& t : in_t) hipLaunchKernelGGL((k_slots_scatter<T>), dim3(n, t.n), dim3(256), 0, stream, t, (const int*)slot_idx(), n, (int)cfg.batch, 1);
             if ((rc = in.mpc_launch_load((const T*)xActual + (size_t)c0 * NX, (const T*)xGoal + (size_t)c0 * NX, shift + c0, clear_vars, full_rollout, &b,
                                          slot_idx(), (int)cfg.batch))) break;

@@ -410,6 +410,62 @@ class Solver:
         self.lib.pddp_clear_goal_trajectory_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._chk(self.lib.pddp_clear_goal_trajectory_problems(self.h, idx.size, _p(idx)))
 
+    # ---- goal paths (pendulum, cart-pole, quadrotor): a device-resident reference per problem, windowed into the goal trajectory table by every control cycle
+    GOAL_PATH_HOLD, GOAL_PATH_WRAP = 1, 2
+
+    def reserve_goal_path(self, capacity):
+        """pddp_reserve_goal_path: room for `capacity` path rows per problem (once per handle; the same capacity again is a no-op)."""
+        self.lib.pddp_reserve_goal_path.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.pddp_reserve_goal_path(self.h, int(capacity)))
+
+    def goal_path_capacity(self):
+        """pddp_goal_path_capacity: rows per problem, 0 before reserve_goal_path; plants 1-3 only."""
+        self.lib.pddp_goal_path_capacity.argtypes = [C.c_void_p]
+        rc = self.lib.pddp_goal_path_capacity(self.h)
+        if rc < 0:
+            self._chk(rc)
+        return rc
+
+    def _path_dtype(self, who, a):
+        if not isinstance(a, np.ndarray) or a.dtype != self.dtype:
+            raise PddpError(f"{who}: the rows must be a numpy array of the handle's element type {self.dtype} (got {getattr(a, 'dtype', type(a).__name__)})")
+
+    def set_goal_path_problems(self, idx, path, mode, cursor=None):
+        """pddp_set_goal_path_problems: path [len(idx)][len][n] in the handle's element type (not converted), one mode (GOAL_PATH_HOLD / GOAL_PATH_WRAP) and one length for
+        the named slots, cursor [len(idx)] (None: 0).  The goal of knot k is path[min(cursor + k, len - 1)] (hold) or path[(cursor + k) % len] (wrap); every control cycle
+        moves the cursor on by the slot's shift.  The window is in the goal trajectory table when the call returns."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        self._path_dtype("set_goal_path_problems", path)
+        if path.ndim != 3 or path.shape[0] != idx.size or path.shape[2] != self.n or path.shape[1] < 1:
+            raise PddpError(f"set_goal_path_problems: {idx.size} slots need rows of shape ({idx.size}, len, {self.n}), got {path.shape}")
+        path = np.ascontiguousarray(path)
+        if cursor is not None:
+            cursor = np.ascontiguousarray(cursor, dtype=np.int32).ravel()
+            if cursor.size != idx.size:
+                raise PddpError(f"set_goal_path_problems: {idx.size} slots need {idx.size} cursors, got {cursor.size}")
+        self.lib.pddp_set_goal_path_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_goal_path_problems(self.h, idx.size, _p(idx), int(path.shape[1]), int(mode), None if cursor is None else _p(cursor), _p(path)))
+
+    def set_goal_path_cursor_problems(self, idx, cursor):
+        """pddp_set_goal_path_cursor_problems: the named slots' cursors (each inside its path) and their windows rewritten."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        cursor = np.ascontiguousarray(cursor, dtype=np.int32).ravel()
+        if cursor.size != idx.size:
+            raise PddpError(f"set_goal_path_cursor_problems: {idx.size} slots need {idx.size} cursors, got {cursor.size}")
+        self.lib.pddp_set_goal_path_cursor_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_goal_path_cursor_problems(self.h, idx.size, _p(idx), _p(cursor)))
+
+    def get_goal_path_problems(self, idx, rows=True):
+        """pddp_get_goal_path_problems: (len, mode, cursor [len(idx)] int32, path [len(idx)][capacity][n] with the rows >= len zero, or None with rows=False).  A slot
+        without a path answers 0, 0, 0."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        cap = self.goal_path_capacity()
+        ln, mode, cur = (np.zeros(idx.size, np.int32) for _ in range(3))
+        path = np.zeros((idx.size, cap, self.n), self.dtype) if rows else None
+        self.lib.pddp_get_goal_path_problems.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        self._chk(self.lib.pddp_get_goal_path_problems(self.h, idx.size, _p(idx), _p(ln), _p(mode), _p(cur), None if path is None else _p(path)))
+        return ln, mode, cur, path
+
     def solve(self, x0, u0, xGoal, clear_vars=1, ignore_first_defect=1, max_sweeps=None, chunk=8, **load_kw):
         """load -> iterate until every problem has exited -> store (the shape of runiLQR_GPU)."""
         self.load(x0, u0, xGoal, clear_vars, ignore_first_defect, **load_kw)
