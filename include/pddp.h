@@ -350,6 +350,39 @@ int pddp_get_goal_path_problems(pddp_handle h, int count, const int* idx, int* l
  * mover kernel in front of the following control cycles / stop (-1: keep); it changes nothing of what the calls compute or launch.  ms, when not
  * NULL, receives the last timed launch's stream time in ms (0 when none was timed). */
 int pddp_goal_path_profile(pddp_handle h, int timing, float* ms);
+/* Per-problem horizon times of the same plants (pendulum, cart-pole, quadrotor).  Every problem of such a handle has
+ * a horizon time in seconds; until a setter call names it, it is config.total_time.  The time step of a problem is
+ * (T)(total_time / (N - 1)) in the handle's element type T -- the expression the handle-wide step is formed with --, so a problem given t
+ * computes the same bits as a handle created with config.total_time = t.  Robots with different control periods, or one problem at a
+ * ladder of horizon durations, share one batch.
+ * Timing is that of pddp_set_diag_cost_problems: a horizon time is in force for the following loads, solves and control cycles; [A B] and
+ * the trajectory already in a slot are NOT rebuilt by the call; problems that are not named keep their times; running problems in other
+ * slots are untouched.  There is no clear call: setting config.total_time again is how a problem returns to the default.
+ * The first setter call gives the handle a device table [batch] of steps in its element type, every entry the handle-wide step; a handle
+ * without a goal table and a table of diagonal cost records gets both, the way the first pddp_set_goal_trajectory_problems call creates
+ * them (no problem flagged, every cost row the built-in record); the captured sweep graph is dropped once.  Later calls only write
+ * entries (on the solver's stream, one synchronisation before the call returns).  A handle that never calls the setter launches exactly
+ * the kernels and arguments it launches without these entry points.
+ * pddp_get_horizon_time_problems: total_time[i] is the time of problem idx[i] as it was given (a host copy of the doubles),
+ * time_step[i] its step as the kernels see it, read back from the device table and widened to double; before the first setter call
+ * config.total_time and the handle-wide step.  Either output may be NULL.  pddp_get_config keeps reporting the handle-wide time.
+ * EVERYTHING MEASURED IN KNOTS STAYS IN KNOTS OF THE PROBLEM'S OWN STEP: shift[b] of pddp_mpc_solve / pddp_mpc_load and of the named-slot
+ * calls moves problem b's previous solution by shift[b] of ITS knots (shift[b] times its own step in seconds), and the cursor of a goal
+ * path advances by the same number of rows -- a path's rows are spaced by its problem's step.  pddp_load_problems,
+ * pddp_mpc_solve_problems and pddp_mpc_load_problems run the named slots with their own times; nothing is written back.
+ * THE HANDLE-WIDE STEP REMAINS where there is no problem index: pddp_plant_eval (what 2 and 3) and pddp_simulate take a host plan and
+ * integrate / interpolate with config.total_time / (N - 1) whatever the table holds.  pddp_simulate_batch interpolates every problem's
+ * plan with one knot spacing per launch: on a handle that has a step table it returns PDDP_EINVAL (a refusal, not a silently wrong
+ * interpolation); on a handle without one it works as before.
+ * PDDP_EINVAL, with the handle unchanged: plants 4 and 5; count < 1; a NULL idx; (setter) a NULL total_time; an index outside
+ * [0, batch) or named twice; (setter) a time that is not finite or not > 0, or whose step rounded to the element type is not finite or
+ * not a normal positive number.  The handle need not be loaded.
+ * A first setter call whose device allocation or transfer fails (PDDP_ENOMEM / PDDP_ENODEVICE) leaves no step table and every time at
+ * the default, but may leave the goal table and the cost table it created first (no problem flagged, built-in rows, the captured graph
+ * dropped): the handle computes what it computed before, and the call can be repeated. */
+int pddp_set_horizon_time_problems(pddp_handle h, int count, const int* idx, const double* total_time /* [count] seconds */);
+int pddp_get_horizon_time_problems(pddp_handle h, int count, const int* idx, double* total_time /* [count], may be NULL */,
+                                   double* time_step /* [count], may be NULL: the step as the kernels see it, widened */);
 /* ---- the lock-step experiment around the solver ------------------------- */
 /* simulateForward<T, SUBSTEPS> (examples/WAFR_MPC_examples.cu:111-139): the simulated robot of the lock-step MPC experiment.  Starting
  * from xActual at plant time t0_us (the plan's t0), integrates the plant IN DOUBLE for elapsed_us in `substeps` steps under the trajectory

@@ -52,7 +52,7 @@ PDDP_HD FpArgs<T> fp_args(const Buffers<T>& b, const Dims& dm, int pb, int a_idx
     a.ucur = b.ucur + (size_t)pb * N * NU; a.dcur = b.dcur + (size_t)pb * N * NX;
     a.KT = b.KT + (size_t)pb * N * NX * NU; a.du = b.du + (size_t)pb * N * NU;
     a.ApBK = b.ApBK + (size_t)pb * N * NX * NX; a.Bdu = b.Bdu + (size_t)pb * N * NX;
-    a.alpha = b.alpha[a_idx]; a.dt = dt; a.segx = segx; a.dnorm = dnorm;
+    a.alpha = b.alpha[a_idx]; a.dt = problem_dt<P, T>(b, pb, dt); a.segx = segx; a.dnorm = dnorm;      // (dt: on a StepTab plant the problem's own step, read once per rollout)
     a.xt = b.xTarget + (size_t)pb * NX; a.segJ = segJ; a.tshift = b.tshift[pb];
     return a;
 }
@@ -124,7 +124,7 @@ PDDP_HD void nis_body(const Wave& w, NisScratch<P, INTEG, T>& s, const Buffers<T
         wsync();
     }
     P::load_model(w, s.plant, reinterpret_cast<const typename P::Model*>(b.model));
-    nis_knot<P, INTEG, T>(w, s, dm, k, xc, uc, goal_at(problem_goal<P, T>(b, pb, N), k), cw, dt,      // (a goal trajectory: row k of the problem's own base and stride, plants.hpp)
+    nis_knot<P, INTEG, T>(w, s, dm, k, xc, uc, goal_at(problem_goal<P, T>(b, pb, N), k), cw, problem_dt<P, T>(b, pb, dt),      // (a goal trajectory: row k of the problem's own base and stride; a step table: the problem's own step -- plants.hpp)
                           b.AB + ((size_t)pb * N + k) * NX * NM, b.H + ((size_t)pb * N + k) * NM * NM, b.g + ((size_t)pb * N + k) * NM,
                           b.xTarget + (size_t)pb * NX, b.tshift[pb], mode == 1 ? b.costk + (size_t)pb * N + k : nullptr, mode == 1);
 }

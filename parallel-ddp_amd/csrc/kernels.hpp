@@ -517,6 +517,9 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
         if constexpr (IsGoalTab<P>::value) { if (gt_on) (&sg.ro.xg[0][0])[lane] = rxg; }
     };
     fetch(0); put(stage[0]); wsync();
+    // a step table (StepTab, plants.hpp): this lane's problem's own step, ONE load in front of the step loop into the register the scalar argument would occupy -- a load
+    // inside the step would queue behind the previous step's stores like every other per-lane load here.  (pb is clamped: a lane past the batch reads entry batch - 1)
+    const T dtl = problem_dt<P, T>(b, pb, dt);
     T cost_k[kTsMaxN];
     T x[NX], u[NU];
     PDDP_UNROLL for (int i = 0; i < NX; i++) x[i] = stage[0].ro.xp[grp][i];
@@ -537,7 +540,7 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
         }
         if constexpr (IsGoalTab<P>::value) cost_k[k] = P::cost(cw, x, u, sc.ro.xg[grp], k, N);      // knot k's goal, from the stage
         else cost_k[k] = P::cost(cw, x, u, xg, k, N);
-        cf_integrator_step<P, INTEG, T>(xn, x, u, dt);
+        cf_integrator_step<P, INTEG, T>(xn, x, u, dtl);
         put(stage[(k + 1) & 1]); wsync();
         T rec[REC];                                         // this knot's record: the state the step started from and its control
         PDDP_UNROLL for (int i = 0; i < NX; i++) rec[i] = x[i];
@@ -659,6 +662,7 @@ template <typename P> struct GradZeroCols { static constexpr unsigned value = 0u
 template <typename T> struct GradZeroCols<QuadPlant<T>> { static constexpr unsigned value = 0x1C7u; };                  // x y z and their rates (plants/dynamics_quad.cuh:75-169 never writes them; tests/test_closed_form_pins.py)
 template <typename B, typename T> struct GradZeroCols<DiagTab<B, T>> : GradZeroCols<B> {};                               // (the same dynamics)
 template <typename B, typename T> struct GradZeroCols<GoalTab<B, T>> : GradZeroCols<B> {};
+template <typename B, typename T> struct GradZeroCols<StepTab<B, T>> : GradZeroCols<B> {};
 template <typename P> struct GradCols {
     static constexpr int NM = P::NX + P::NU;
     static constexpr unsigned zero = GradZeroCols<P>::value;
@@ -669,7 +673,7 @@ template <typename P> struct GradCols {
 template <typename P, typename T, int KB>
 struct NisKbLds { T d[GradCols<P>::count * P::NPOS][3][KB + 1]; };
 template <typename P, typename T, int KB>
-__global__ __launch_bounds__(64) void k_nis_kb(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int mode, int batch) {
+__global__ __launch_bounds__(64) void k_nis_kb(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt_h, int mode, int batch) {      // dt_h: the handle-wide step; a lane integrates with problem_dt of its unit's problem
     constexpr int NP = P::NPOS, NX = P::NX, NU = P::NU, NM = NX + NU, ND = NP * NM;
     using GC = GradCols<P>;
     constexpr bool kStageLanes = 3 * KB <= 64;          // phase 1 with one lane per (stage, knot)
@@ -682,6 +686,7 @@ __global__ __launch_bounds__(64) void k_nis_kb(Buffers<T> b, Dims dm, CostWeight
         const int inst = blockIdx.x * KB + j;
         if (lane < (kStageLanes ? 3 * KB : KB) && inst < total) {
             const int pb = inst / N, k = inst - pb * N;
+            const T dt = problem_dt<P, T>(b, pb, dt_h);          // (a step table: this (stage, knot) lane's problem's entry, read once)
             const SolverState<T>& st = b.state[pb];
             const bool moved = mode == 1 || st.accepted == 1;
             if (moved) {
@@ -779,6 +784,7 @@ __global__ __launch_bounds__(64) void k_nis_kb(Buffers<T> b, Dims dm, CostWeight
         const int j = rnd * 4 + grp, inst = blockIdx.x * KB + j;
         if (inst >= total || ky >= NM) continue;
         const int pb = inst / N, k = inst - pb * N;
+        const T dt = problem_dt<P, T>(b, pb, dt_h);              // (the column factors below are formed from the unit's problem's own step)
         const SolverState<T>& st = b.state[pb];
         if (!(mode == 1 || (st.accepted == 1 && !st.done))) continue;
         if constexpr (!P::kPluginCost) {

@@ -61,12 +61,13 @@ PDDP_HD void mpc_gather_last_knot(const Wave& w, T* dst, const T* src, int per, 
 // form copies them: shift == 0 (in place a no-op for P, p, Pp, pp, d, u, KT), knots N-2 and N-1 of u / KT, knot N-1 of d, P, p, Pp, pp.  (Both halves of xb are
 // written whole in either form.)  With GATHER = false every condition and argument below folds to what the in-place kernel always had.
 template <typename P, int INTEG, typename T, int V = -1, bool GATHER = false>
-PDDP_HD void mpc_load_body(const Wave& w, MpcScratch<P, T>& s, const Buffers<T>& b, const MpcBuffers<T>& mb, const Dims& dm, T dt, int pb,
+PDDP_HD void mpc_load_body(const Wave& w, MpcScratch<P, T>& s, const Buffers<T>& b, const MpcBuffers<T>& mb, const Dims& dm, T dt_h, int pb,
                            const T* xActual, int shift, int clear_vars, int full_rollout, int wave_id = 0, int nwaves = 1, float* pipe = nullptr,
                            const MpcPrev<T>* prev = nullptr) {
     // wave_id / nwaves: the workgroup's waves share the shifting and the fall-back copies (task t runs on wave t % nwaves); the rollout is wave 0's
     constexpr int NX = P::NX, NU = P::NU, NM = NX + NU;
     const int N = dm.N;
+    const T dt = problem_dt<P, T>(b, pb, dt_h);             // (a step table: the warm-start rollout integrates with the problem's own step; pb is uniform, one scalar load)
     const int cur = GATHER ? prev->cur : b.state[pb].cur;
     T* x0 = b.xb + ((size_t)pb * 2 + 0) * N * NX;          // after the load: the rolled-out trajectory
     T* x1 = b.xb + ((size_t)pb * 2 + 1) * N * NX;          // after the load: the shifted previous trajectory (the reference's d_xp)

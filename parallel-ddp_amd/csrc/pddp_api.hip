@@ -140,6 +140,11 @@ extern "C" int pddp_goal_trajectory_size(pddp_handle h) {
 extern "C" int pddp_set_goal_trajectory_problems(pddp_handle h, int count, const int* idx, const void* G) { IMPL(h); return s->set_goal_trajectory_problems(count, idx, G); }
 extern "C" int pddp_get_goal_trajectory_problems(pddp_handle h, int count, const int* idx, void* G, int* has) { IMPL(h); return s->get_goal_trajectory_problems(count, idx, G, has); }
 extern "C" int pddp_clear_goal_trajectory_problems(pddp_handle h, int count, const int* idx) { IMPL(h); return s->clear_goal_trajectory_problems(count, idx); }
+// per-problem horizon times of the same plants (horizon_time_table.hpp): the handle checks every argument before it is touched
+extern "C" int pddp_set_horizon_time_problems(pddp_handle h, int count, const int* idx, const double* total_time) { IMPL(h); return s->set_horizon_time_problems(count, idx, total_time); }
+extern "C" int pddp_get_horizon_time_problems(pddp_handle h, int count, const int* idx, double* total_time, double* time_step) {
+    IMPL(h); return s->get_horizon_time_problems(count, idx, total_time, time_step);
+}
 // goal paths of the same plants (goal_path_table.hpp): the handle checks every argument before it is touched
 extern "C" int pddp_reserve_goal_path(pddp_handle h, int capacity) { IMPL(h); return s->reserve_goal_path(capacity); }
 extern "C" int pddp_goal_path_capacity(pddp_handle h) { IMPL(h); return s->goal_path_capacity(); }

@@ -298,6 +298,26 @@ PDDP_HD auto problem_goal(const Buffers<T>& b, int pb, int N) {
     } else return (const T*)(b.xGoal + (size_t)pb * P::NX);
 }
 
+// ---- per-problem horizon times of the same plants (pddp_set_horizon_time_problems) ----
+// Buffers::dtab is null, or a table [batch] of time steps in the handle's element type (horizon_time_table.hpp: (T)(total_time / (N - 1)) of the problem's own horizon
+// time).  StepTab<B, T> is GoalTab<B, T> -- the same cost routines, records and goals -- for the handles that have such a table: the top layer of the chain, a policy
+// of its own once more, so that the instantiations on B, DiagTab<B, T> and GoalTab<B, T> are the ones they always were.  What differs is the step a kernel that
+// integrates hands to the integrator: problem_dt gives the kernel argument on every other policy and the problem's own entry on StepTab.  Kernels that read no step
+// have no StepTab instantiation.
+template <typename B, typename T>
+struct StepTab : GoalTab<B, T> {
+    template <typename U> using Rebind = StepTab<typename B::template Rebind<U>, U>;
+};
+template <typename B, typename T> struct IsDiagTab<StepTab<B, T>> { static constexpr bool value = true; };
+template <typename B, typename T> struct IsGoalTab<StepTab<B, T>> { static constexpr bool value = true; };
+template <typename P> struct IsStepTab { static constexpr bool value = false; };
+template <typename B, typename T> struct IsStepTab<StepTab<B, T>> { static constexpr bool value = true; };
+template <typename P, typename T>
+PDDP_HD T problem_dt(const Buffers<T>& b, int pb, T dt) {
+    if constexpr (IsStepTab<P>::value) return b.dtab[pb];
+    else return dt;
+}
+
 // A scalar plug-in's gradient routine also returns qdd; the kernel families build the midpoint / RK3 stage states from that qdd (serial paths) or from the dynamics routine's
 // (the staged three-lane path of integrators.hpp), so the two have to be the SAME numbers -- the reference's plug-ins call dynamics() inside dynamicsGradient.  Checked on the
 // host instantiation when a handle of a user plant is created.

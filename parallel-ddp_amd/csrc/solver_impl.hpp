@@ -9,6 +9,7 @@
 #include "diag_cost_table.hpp"
 #include "goal_traj_table.hpp"
 #include "goal_path_table.hpp"
+#include "horizon_time_table.hpp"
 #include "mpc_slots.hpp"
 #include "mpc_record.hpp"
 #include "tl_launch.hpp"
@@ -281,7 +282,7 @@ struct Solver : SolverBase {
         if constexpr (P::PLANT != 4 && P::kScalarPlugin && (64 / AA) * P::NX <= 64) {
             const unsigned B = cfg.batch;
             const dim3 grid((B + 64 / AA - 1) / (64 / AA));
-            if (rollouts) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B); });
+            if (rollouts) with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B); });
             else hipLaunchKernelGGL((k_sweep_cf<P, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B);
         }
     }
@@ -330,10 +331,10 @@ struct Solver : SolverBase {
             break;
         case kFpKernCf: if (cfg.A == 16) launch_cf<16>(s, true); else if (cfg.A == 8) launch_cf<8>(s, true); break;
         case kFpKernTs:           // (the arm has its own families: no thread-serial instantiation of its cooperative bodies)
-            if constexpr (P::PLANT != 4) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, L.seed == 2 ? 1 : 0); });
+            if constexpr (P::PLANT != 4) with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, L.seed == 2 ? 1 : 0); });
             break;
         case kFpKernCoop:
-            with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(A_all, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, L.seed); });
+            with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(A_all, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, L.seed); });
             break;
         }
         if constexpr (P::PLANT != 4) { if (L.cand_to_xw && b.xw) hipLaunchKernelGGL((k_cand_to_xw<P, T>), dim3((unsigned)(((size_t)B * cfg.N * cfg.A + 255) / 256)), dim3(256), 0, s, b, dm, (int)B); }
@@ -363,12 +364,12 @@ struct Solver : SolverBase {
             }
             break;
         case kNisTs:
-            if constexpr (P::PLANT != 4) with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis_ts<Q, INTEG, T>), dim3((B * cfg.N + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); });
+            if constexpr (P::PLANT != 4) with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis_ts<Q, INTEG, T>), dim3((B * cfg.N + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); });
             break;
         case kNisKb:
             if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16 && INTEG == 3 && P::kScalarPlugin) {
                 const int units = (int)(B * cfg.N);
-                with_cost_plant([&](auto pl) {
+                with_step_plant([&](auto pl) {
                     using Q = decltype(pl);
                     if (plan.kb_nis == 16) hipLaunchKernelGGL((k_nis_kb<Q, T, 16>), dim3((units + 15) / 16), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
                     else if (plan.kb_nis == 20) hipLaunchKernelGGL((k_nis_kb<Q, T, 20>), dim3((units + 19) / 20), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
@@ -379,7 +380,7 @@ struct Solver : SolverBase {
             break;
         case kNisGl:
             if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) {
-                with_cost_plant([&](auto pl) {
+                with_step_plant([&](auto pl) {
                     using Q = decltype(pl);
                     if (plan.gl_nis8) hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 8>), dim3((B * cfg.N + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
                     else hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 16>), dim3((B * cfg.N + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
@@ -388,7 +389,7 @@ struct Solver : SolverBase {
             break;
         case kNisCoop:
             if constexpr (P::PLANT == 4) { if (b.cwt) { hipLaunchKernelGGL((k_nis<P, INTEG, T, true>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); break; } }
-            with_cost_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis<Q, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); });
+            with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis<Q, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); });
             break;
         }
     }
@@ -662,6 +663,12 @@ struct Solver : SolverBase {
         if constexpr (kDiagCost) { if (b.cwt) { f(DiagTab<P, T>{}); return; } }
         f(P{});
     }
+    // the kernels that integrate (rollouts, setup, warm start): StepTab<P, T> for a handle with a table of per-problem time steps (it always has the other two tables),
+    // with_cost_plant's choice otherwise -- a handle without the table launches the instantiations it always launched
+    template <typename F> void with_step_plant(F&& f) {
+        if constexpr (kDiagCost) { if (b.dtab) { f(StepTab<P, T>{}); return; } }
+        with_cost_plant(f);
+    }
     int diag_refuse(const char* who) { return fail(PDDP_EINVAL, std::string(who) + ": diagonal cost records belong to the pendulum, cart-pole and quadrotor (plants 1-3); the arm has pddp_set_cost_problems, a plug-in plant its own cost file"); }
     // first setter call: the table, every row the built-in record; b.cwt; the captured graph goes once (other kernels, another argument)
     int ensure_diag_table() {
@@ -799,6 +806,72 @@ struct Solver : SolverBase {
             if (!gf_stage[i]) goal_rows_from_xgoal<T>(gt_stage.data() + (size_t)i * NX, cfg.N, NX, G + (size_t)i * len);      // no trajectory: what the cost reads, xGoal at every knot
             if (has) has[i] = gf_stage[i] ? 1 : 0;
         }
+        return 0;
+    }
+    // ---- per-problem horizon times of the same plants (horizon_time_table.hpp, plants.hpp StepTab): pddp_set_horizon_time_problems / pddp_get_horizon_time_problems
+    // A table [batch] of time steps from the first setter call on; b.dtab is what the kernels see.  With it every kernel that integrates runs in its StepTab instantiation
+    // (with_step_plant) and takes problem pb's step from entry pb; `dt`, the handle-wide step, stays the argument of every launch (and the step of pddp_plant_eval and
+    // pddp_simulate, which have no problem index).  A handle with a step table always has the goal table and the table of diagonal records too (StepTab is layered on
+    // GoalTab), created through ensure_goal_table: no problem flagged, the built-in rows.  The host keeps the times as they were given (ht_host).
+    DeviceBuf d_dtab;
+    T* dtab_rows() const { return d_dtab.template as<T>(); }
+    std::vector<double> ht_host;                   // [batch] horizon times in seconds as given; cfg.total_time for a problem no call has named
+    std::vector<T> ht_stage;                       // host steps of the call in flight (the call waits for the stream before it returns)
+    int horizon_refuse(const char* who) { return fail(PDDP_EINVAL, std::string(who) + ": per-problem horizon times belong to the pendulum, cart-pole and quadrotor (plants 1-3)"); }
+    // first setter call: the goal table and the cost table if there are none, the step table with the handle-wide step in every entry; b.dtab; the captured graph goes
+    // once (other kernels).  Everything of the step table is released again if a step fails.  What ensure_goal_table() created before that step stays: a failed
+    // allocation or transfer here (PDDP_ENOMEM / PDDP_ENODEVICE, never PDDP_EINVAL -- the arguments were checked before) leaves the handle with the goal table and the
+    // cost table of a first pddp_set_goal_trajectory_problems call (no problem flagged, built-in rows, the graph dropped), which compute what it computed without them
+    // (tests/test_goal_trajectory.py, tests/test_diag_costs.py), and with no step table; the call can be repeated.
+    int ensure_step_table() {
+        if (b.dtab) return 0;
+        if constexpr (kDiagCost) {
+            if (int rc = ensure_goal_table()) return rc;
+            if (int rc = reserve(d_dtab, (size_t)cfg.batch * sizeof(T), "hipMalloc failed for the per-problem time steps")) return rc;
+            ht_stage.assign((size_t)cfg.batch, time_step<T>(cfg));
+            hipError_t e = hipMemcpyAsync(d_dtab.ptr, ht_stage.data(), (size_t)cfg.batch * sizeof(T), hipMemcpyHostToDevice, stream);
+            const hipError_t es = hipStreamSynchronize(stream);     // (nothing in flight reads the old argument set)
+            if (e == hipSuccess) e = es;
+            if (e == hipSuccess && fp_lds > 48 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fp<StepTab<P, T>, INTEG, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp_lds);
+            if (e != hipSuccess) { d_dtab.release(); return fail(PDDP_ENODEVICE, std::string("per-problem time steps: creating the table failed: ") + hipGetErrorString(e)); }
+            ht_host.assign((size_t)cfg.batch, cfg.total_time);
+            b.dtab = dtab_rows();
+            drop_graph();
+        }
+        return 0;
+    }
+    int set_horizon_time_problems(int count, const int* idx, const double* total_time) override {
+        if (!kDiagCost) return horizon_refuse("pddp_set_horizon_time_problems");
+        const std::string complaint = horizon_times_complaint<T>(count, idx, total_time, cfg.batch, cfg.N);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_horizon_time_problems: " + complaint);
+        if (int rc = ensure_step_table()) return rc;
+        ht_stage.resize((size_t)count);
+        for (int i = 0; i < count; i++) ht_stage[i] = horizon_time_step<T>(total_time[i], cfg.N);
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int run) {     // contiguous runs of slots in one transfer each; problems that are not named keep theirs
+            if (e == hipSuccess) e = hipMemcpyAsync(dtab_rows() + idx[first], ht_stage.data() + first, (size_t)run * sizeof(T), hipMemcpyHostToDevice, stream);
+        });
+        const hipError_t es = hipStreamSynchronize(stream);
+        if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string("pddp_set_horizon_time_problems: transfer of entries failed: ") + hipGetErrorString(e != hipSuccess ? e : es));
+        for (int i = 0; i < count; i++) ht_host[idx[i]] = total_time[i];
+        return 0;
+    }
+    int get_horizon_time_problems(int count, const int* idx, double* total_time, double* step) override {
+        if (!kDiagCost) return horizon_refuse("pddp_get_horizon_time_problems");
+        const std::string complaint = horizon_times_complaint<T>(count, idx, nullptr, cfg.batch, cfg.N, false);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_get_horizon_time_problems: " + complaint);
+        if (total_time) for (int i = 0; i < count; i++) total_time[i] = b.dtab ? ht_host[idx[i]] : cfg.total_time;
+        if (!step) return 0;
+        ht_stage.assign((size_t)count, time_step<T>(cfg));          // (no table: the handle-wide step)
+        if (b.dtab) {
+            hipError_t e = hipSuccess;
+            for_each_slot_run(count, idx, [&](int first, int run) {
+                if (e == hipSuccess) e = hipMemcpyAsync(ht_stage.data() + first, dtab_rows() + idx[first], (size_t)run * sizeof(T), hipMemcpyDeviceToHost, stream);
+            });
+            const hipError_t es = hipStreamSynchronize(stream);
+            if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string("pddp_get_horizon_time_problems: transfer failed: ") + hipGetErrorString(e != hipSuccess ? e : es));
+        }
+        for (int i = 0; i < count; i++) step[i] = (double)ht_stage[i];
         return 0;
     }
     // ---- goal paths of the same plants (goal_path_table.hpp, k_goal_window in kernels.hpp): pddp_reserve_goal_path / pddp_set_goal_path_problems / ..._cursor_problems / pddp_get_...
@@ -1006,6 +1079,14 @@ struct Solver : SolverBase {
     template <int V> void launch_mpc_load(int clear_vars, int full_rollout, const Buffers<T>* from, const int* d_idx, int from_batch) {
         const dim3 grid(cfg.batch), block(V < 0 ? 256 : 512);
         const int tsm = (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0;
+        if constexpr (kDiagCost) {
+            if (b.dtab) {            // per-problem time steps: the warm-start rollout in its StepTab instantiation (the kernel reads no cost: P itself on every other handle)
+                using Q = StepTab<P, T>;
+                if (from) hipLaunchKernelGGL((k_mpc_load_slots<Q, INTEG, T, V>), grid, block, 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
+                else hipLaunchKernelGGL((k_mpc_load<Q, INTEG, T, V>), grid, block, 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
+                return;
+            }
+        }
         if (from) hipLaunchKernelGGL((k_mpc_load_slots<P, INTEG, T, V>), grid, block, 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
         else hipLaunchKernelGGL((k_mpc_load<P, INTEG, T, V>), grid, block, 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
     }
@@ -1148,6 +1229,10 @@ struct Solver : SolverBase {
             if (int rc = in.reserve_goal_table(slot_chunk())) return rc;
             in.b.gtab = in.gtab_rows(); in.b.gflag = in.gflag_rows();
         }
+        if (b.dtab && !in.b.dtab) {                                  // per-problem time steps: the same, one entry per slot of the chunk
+            if (int rc = in.reserve(in.d_dtab, (size_t)slot_chunk() * sizeof(T), "hipMalloc failed for the intake area's time steps")) return rc;
+            in.b.dtab = in.dtab_rows();
+        }
         if (!b.ABc) { in.b.ABc = nullptr; in.b.Hc = nullptr; }      // the handle left the compact layouts (ab_keep_reference_layout): so does its intake
         return ensure_slot_idx();
     }
@@ -1188,6 +1273,9 @@ struct Solver : SolverBase {
             const size_t gb = goal_len() * sizeof(T);
             if (!slot_add(fetch, in.gtab_rows(), gtab_rows(), gb, gb, gb, kSlotCopy) || !slot_add(fetch, in.gflag_rows(), gflag_rows(), sizeof(int), sizeof(int), sizeof(int), kSlotCopy))
                 return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
+        }
+        if (b.dtab) {                                                // ... and their time steps
+            if (!slot_add(fetch, in.dtab_rows(), dtab_rows(), sizeof(T), sizeof(T), sizeof(T), kSlotCopy)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
         }
         const size_t N = cfg.N;
         const int C = slot_chunk();
@@ -1249,8 +1337,9 @@ struct Solver : SolverBase {
     bool cycle_tables(std::vector<SlotTable>& in_t, std::vector<SlotTable>& out_t) {
         const Solver& in = *intake;
         const bool gt = b.gtab != nullptr;
-        const MpcSlotSide<T> is{b.cwt ? in.cwt_rows() : nullptr, in.d_xActual, in.d_goal_in, in.d_shift, gt ? in.gtab_rows() : nullptr, gt ? in.gflag_rows() : nullptr},
-                             hs{b.cwt ? cwt_rows() : nullptr, d_xActual, d_goal_in, d_shift, gt ? gtab_rows() : nullptr, gt ? gflag_rows() : nullptr};
+        const bool st = b.dtab != nullptr;
+        const MpcSlotSide<T> is{b.cwt ? in.cwt_rows() : nullptr, in.d_xActual, in.d_goal_in, in.d_shift, gt ? in.gtab_rows() : nullptr, gt ? in.gflag_rows() : nullptr, st ? in.dtab_rows() : nullptr},
+                             hs{b.cwt ? cwt_rows() : nullptr, d_xActual, d_goal_in, d_shift, gt ? gtab_rows() : nullptr, gt ? gflag_rows() : nullptr, st ? dtab_rows() : nullptr};
         return mpc_slot_tables<NX, NU, T>(in_t, out_t, in.b, in.mb, is, b, mb, hs, cfg.N, cfg.M, cfg.A, cfg.max_iter, cfg.ee_cost, table_record_len());
     }
     // pddp_mpc_slots_profile (measurement): HIP events around the in stage (movers + load kernel), the cycle and the out stage of every chunk
@@ -1456,6 +1545,9 @@ struct Solver : SolverBase {
                        double* avg_err, int* failed) override {
         using In = PlantSimBatchIn<PD, T>; using Out = PlantSimBatchOut<PD, T>;
         const size_t B = cfg.batch, N = cfg.N;
+        if (b.dtab)                                                  // (the kernel interpolates every plan with ONE knot spacing, step_us: a refusal, not a silently wrong interpolation)
+            return fail(PDDP_EINVAL, "pddp_simulate_batch: this handle has per-problem horizon times (pddp_set_horizon_time_problems), and the batched simulator takes one knot "
+                                     "spacing for the whole launch; simulate such problems with pddp_simulate on a handle of their own horizon time");
         if ((x != nullptr) != (u != nullptr) || (x != nullptr) != (KT != nullptr))
             return fail(PDDP_EINVAL, "pddp_simulate_batch: x, u and KT are either all given (host plans) or all NULL (the solution the handle holds)");
         if (substeps < 1) return fail(PDDP_EINVAL, "pddp_simulate_batch: substeps >= 1");

@@ -75,6 +75,7 @@ struct Buffers {
     const T* cwt;        // [B][5 | 9] per-problem cost weights of the arm (plants.hpp cost_weights_at); null: every problem carries the handle-wide record, a kernel argument
     const T* gtab;       // [B][N][n] per-knot goal trajectories of the pendulum, cart-pole and quadrotor (plants.hpp GoalTab); null: every problem's goal is xGoal[b]
     const int* gflag;    // [B] with gtab: 1 = the problem's cost reads its rows of gtab, 0 = it reads xGoal[b]
+    const T* dtab = nullptr;   // [B] per-problem time steps of the same plants (plants.hpp StepTab, problem_dt); null: every problem integrates with the kernel argument dt
 };
 
 // Rows of Buffers::cwt (plants.hpp cost_weights_at): 5 weights of the joint-space cost, 9 of the end-effector cost, in the argument order of pddp_set_cost / pddp_set_cost_ee.

@@ -410,6 +410,27 @@ class Solver:
         self.lib.pddp_clear_goal_trajectory_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._chk(self.lib.pddp_clear_goal_trajectory_problems(self.h, idx.size, _p(idx)))
 
+    # ---- per-problem horizon times (pendulum, cart-pole, quadrotor)
+    def set_horizon_time_problems(self, idx, times):
+        """pddp_set_horizon_time_problems: times[i] seconds (len(idx) doubles) is the horizon time of slot idx[i]; its step is T(times[i] / (N - 1)), what a handle created
+        with total_time = times[i] integrates with.  In force for the following loads, solves and control cycles (follow it with load() or load_problems(idx, ...));
+        the other slots keep theirs."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        if times.size != idx.size:
+            raise PddpError(f"set_horizon_time_problems: {idx.size} slots need {idx.size} times, got {times.size}")
+        self.lib.pddp_set_horizon_time_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_horizon_time_problems(self.h, idx.size, _p(idx), _p(times)))
+
+    def get_horizon_time_problems(self, idx):
+        """pddp_get_horizon_time_problems: (times [len(idx)] seconds as they were given, steps [len(idx)] as the kernels see them, widened to double); config.total_time
+        and the handle-wide step before the first setter call."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        times, steps = np.zeros(idx.size, np.float64), np.zeros(idx.size, np.float64)
+        self.lib.pddp_get_horizon_time_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_get_horizon_time_problems(self.h, idx.size, _p(idx), _p(times), _p(steps)))
+        return times, steps
+
     # ---- goal paths (pendulum, cart-pole, quadrotor): a device-resident reference per problem, windowed into the goal trajectory table by every control cycle
     GOAL_PATH_HOLD, GOAL_PATH_WRAP = 1, 2
 
