@@ -373,7 +373,7 @@ int pddp_goal_path_profile(pddp_handle h, int timing, float* ms);
  * THE HANDLE-WIDE STEP REMAINS where there is no problem index: pddp_plant_eval (what 2 and 3) and pddp_simulate take a host plan and
  * integrate / interpolate with config.total_time / (N - 1) whatever the table holds.  pddp_simulate_batch interpolates every problem's
  * plan with one knot spacing per launch: on a handle that has a step table it returns PDDP_EINVAL (a refusal, not a silently wrong
- * interpolation); on a handle without one it works as before.
+ * interpolation); on a handle without one it works as before.  pddp_simulate_problems (below) is the simulator that takes a slot's own time.
  * PDDP_EINVAL, with the handle unchanged: plants 4 and 5; count < 1; a NULL idx; (setter) a NULL total_time; an index outside
  * [0, batch) or named twice; (setter) a time that is not finite or not > 0, or whose step rounded to the element type is not finite or
  * not a normal positive number.  The handle need not be loaded.
@@ -402,6 +402,36 @@ int pddp_simulate(pddp_handle h, const void* x, const void* u, const void* KT, d
  * pddp_iterate / pddp_mpc_solve / pddp_store reads: the solution arrays are only read. */
 int pddp_simulate_batch(pddp_handle h, const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us, int substeps,
                         const void* goal_xyz, void* xActual_inout, double* avg_err, int* failed);
+/* The simulated robots of NAMED slots, each at its own step: entry i of every [count] argument is the robot of slot idx[i] -- the body of pddp_simulate
+ * unchanged, the plant in double, the control law in the plan's precision.  The cost of a call follows `count`, not `batch`.
+ * PLAN: x / u / KT all NULL: entry i follows the solution slot idx[i] holds on the device (what pddp_store_problems would return for that slot now); all
+ * three given: host plans x [count][N][n], u [count][N][m], KT [count][N][n*m], entry i follows entry i.  A mixture is PDDP_EINVAL.
+ * KNOT SPACING: on a handle with per-problem horizon times (pddp_set_horizon_time_problems) entry i interpolates its plan with
+ * t / (N - 1) * 1000.0 * 1000.0 microseconds, t the horizon time of slot idx[i] as it was given (the doubles pddp_get_horizon_time_problems answers from);
+ * on a handle without a step table t = config.total_time.  Entry i therefore computes, bit for bit, what pddp_simulate computes on a handle created with
+ * config.total_time = t.  (pddp_simulate and pddp_simulate_batch keep the handle-wide step; the latter still refuses a handle with a step table.)
+ * substeps [count], each >= 1: robots with different control periods can integrate with the same sub-step length.  t0_us [count] finite,
+ * elapsed_us [count] >= 0; goal_xyz [count][3] in the handle's dtype (arm only, may be NULL: no error metric); xActual_inout [count][n];
+ * avg_err [count], failed [count] (either may be NULL).  An entry whose time leaves its plan (k >= N - 2 AT ITS OWN SPACING) aborts alone: its state
+ * untouched, error 0, failed 1.
+ * A SLOT MAY BE NAMED MORE THAN ONCE -- unlike the calls that write slots (pddp_load_problems, pddp_mpc_solve_problems, the table setters), which refuse
+ * a duplicate: this call only READS slots, and one plan under many perturbed start states is a legitimate use.  Nothing that belongs to a slot changes:
+ * solution arrays, state records and tables are only read.
+ * family: 0 the library's choice, 1 one wavefront per entry (every plant), 2 one thread per entry (pendulum, cart-pole, quadrotor: many small robots in
+ * flight); the families compute the same bits.
+ * Enqueued on the solver's stream behind whatever is there; per call one transfer up (+ the three plans when they come from the host), one launch, one
+ * transfer back, one synchronisation, on buffers of the call's own that grow with `count` and are released with the handle.
+ * PDDP_EINVAL, with a message that names the call and the handle unchanged: count < 1; NULL idx, t0_us, elapsed_us, substeps or xActual_inout; an index
+ * outside [0, batch); substeps[i] < 1; elapsed_us[i] not >= 0 (NaN included); t0_us[i] not finite; family outside 0..2; family 2 on the arm or a plug-in
+ * plant (plants 4 and 5); NULL plans on a handle that pddp_load / pddp_solve never filled. */
+int pddp_simulate_problems(pddp_handle h, int count, const int* idx,
+                           const void* x, const void* u, const void* KT,      /* [count][N][..] host plans, or all NULL */
+                           const double* t0_us, const double* elapsed_us,     /* [count] */
+                           const int* substeps,                               /* [count], each >= 1 */
+                           const void* goal_xyz,                              /* [count][3], arm only, may be NULL */
+                           void* xActual_inout,                               /* [count][n] */
+                           double* avg_err, int* failed,                      /* [count], may be NULL */
+                           int family);                                       /* 0 library's choice, 1 wave per problem, 2 thread per problem */
 /* compute_eePos_scratch (plants/dynamics_arm.cuh:1953-1960): tool point (x, y, z, roll, pitch, yaw) of `count` states [count][n] -> [count][6]. */
 int pddp_ee_pos(pddp_handle h, int count, const void* x, void* eePos);
 /* The HIP stream every kernel of this handle is enqueued on (a hipStream_t). */

@@ -84,7 +84,8 @@ template <typename T, int PLANT> CostWeights<T> cost_weights_of(const pddp_confi
     return cw;
 }
 template <typename T> T time_step(const pddp_config& c) { return (T)(c.total_time / (c.N - 1)); }      // TIME_STEP, config.cuh:136
-inline double step_us(const pddp_config& c) { return c.total_time / (c.N - 1) * 1000.0 * 1000.0; }      // the same in microseconds (the plant simulator's clock)
+inline double step_us(double total_time, int N) { return total_time / (N - 1) * 1000.0 * 1000.0; }     // the same in microseconds (the plant simulator's clock) ...
+inline double step_us(const pddp_config& c) { return step_us(c.total_time, c.N); }                       // ... of the handle, and of a slot with its own horizon time (pddp_simulate_problems)
 template <typename T> void alpha_table(const pddp_config& c, T* out) { for (int i = 0; i < c.A; i++) out[i] = (T)std::pow(c.alpha_base, (double)i); }   // nisInitHelpers.cuh:829
 
 // The arrays every implementation of a handle registers under a name: visit(name, pointer slot in b / mb, element count) allocates `count` zeroed elements, points the

@@ -1154,6 +1154,46 @@ __global__ __launch_bounds__(64) void k_plant_sim_batch(const void* model, const
     const T* KT = px ? pKT + pb * N * NX * NU : b.KT + pb * N * NX * NU;
     plant_sim_batch_body<PD, INTEG, T>(this_wave(), s, model, in[pb], out[pb], x, u, KT, N, step_us, substeps, has_goal != 0, ee_z);
 }
+// ---- the simulated robots of NAMED slots (pddp_simulate_problems, sim_slots.hpp): entry i follows the plan of slot in[i].slot -- the solution that slot holds, addressed
+// as above, or entry i of the uploaded plans [count][N][...] -- with the knot spacing and the sub-step count of its own record.  Slots are only read, so one slot may
+// stand in many entries.  A slot outside the handle (validated on the host) must not become a stray read: such an entry reports failure and touches nothing else.
+template <typename PD, typename T>
+PDDP_D bool sim_slot_plan(const PlantSimSlotIn<PD, T>& r, PlantSimBatchOut<PD, T>& o, size_t i, const T* px, const T* pu, const T* pKT, const Buffers<T>& b, int N, int batch,
+                          const T*& x, const T*& u, const T*& KT) {
+    constexpr int NX = PD::NX, NU = PD::NU;
+    const int q = r.slot;
+    if (q < 0 || q >= batch) { for (int c = 0; c < NX; c++) o.x[c] = r.x[c]; o.out[0] = 0.0; o.out[1] = 1.0; return false; }
+    const size_t pb = px ? i : (size_t)q;
+    x = px ? px + pb * N * NX : b.xb + (pb * 2 + b.state[pb].cur) * N * NX;
+    u = px ? pu + pb * N * NU : b.ucur + pb * N * NU;
+    KT = px ? pKT + pb * N * NX * NU : b.KT + pb * N * NX * NU;
+    return true;
+}
+// family 1: grid (count), block 64 -- one wavefront per entry, every plant
+template <typename PD, int INTEG, typename T>
+__global__ __launch_bounds__(64) void k_plant_sim_slots(const void* model, const PlantSimSlotIn<PD, T>* __restrict__ in, PlantSimBatchOut<PD, T>* __restrict__ out, const T* px, const T* pu,
+                                                        const T* pKT, Buffers<T> b, int N, int batch, int has_goal, double ee_z) {
+    __shared__ PlantSimScratch<PD, T> s;
+    const size_t i = blockIdx.x;
+    const T *x, *u, *KT;
+    if (!sim_slot_plan<PD, T>(in[i], out[i], i, px, pu, pKT, b, N, batch, x, u, KT)) return;
+    plant_sim_batch_body<PD, INTEG, T>(this_wave(), s, model, in[i], out[i], x, u, KT, N, in[i].step_us, in[i].substeps, has_goal != 0, ee_z);
+}
+// family 2, the closed-form plants with many entries in flight: grid (ceil(count / 64)), block 64, one THREAD per entry -- the same body under the one-lane wave of
+// the thread-serial sweep kernels above (every PDDP_FOR loop serial in index order, `lane == 0` true for every thread: bit for bit what family 1 computes), its scratch
+// in the thread's private memory, no LDS, no barriers.  Trip counts differ between the lanes of a wavefront (sub-step counts and aborts are per entry); the body has no
+// cross-lane operation, and wsync under this wave is a compiler fence.  Plan reads are per thread (uncoalesced by nature); results leave through the thread's own record.
+template <typename PD, int INTEG, typename T>
+__global__ __launch_bounds__(64) void k_plant_sim_ts(const void* model, const PlantSimSlotIn<PD, T>* __restrict__ in, PlantSimBatchOut<PD, T>* __restrict__ out, const T* px, const T* pu,
+                                                     const T* pKT, Buffers<T> b, int N, int batch, int count, int has_goal, double ee_z) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    static_assert(PD::PLANT >= 1 && PD::PLANT <= 3, "the thread-serial simulator belongs to the pendulum, cart-pole and quadrotor");
+    PlantSimScratch<PD, T> s;
+    const T *x, *u, *KT;
+    if (!sim_slot_plan<PD, T>(in[i], out[i], (size_t)i, px, pu, pKT, b, N, batch, x, u, KT)) return;
+    plant_sim_batch_body<PD, INTEG, T>(serial_wave(), s, model, in[i], out[i], x, u, KT, N, in[i].step_us, in[i].substeps, has_goal != 0, ee_z);
+}
 // tool point of `count` states: grid (count), block 64
 template <typename P, typename T>
 __global__ __launch_bounds__(64) void k_ee_pos(const void* model, T ee_z, const T* x, T* out) {

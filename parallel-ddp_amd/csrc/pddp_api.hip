@@ -166,6 +166,11 @@ extern "C" int pddp_simulate_batch(pddp_handle h, const void* x, const void* u, 
     IMPL(h); if (!t0_us || !elapsed_us || !xActual_inout) return fail(PDDP_EINVAL, "pddp_simulate_batch: null t0_us, elapsed_us or xActual_inout");
     return s->simulate_batch(x, u, KT, t0_us, elapsed_us, substeps, goal_xyz, xActual_inout, avg_err, failed);
 }
+// the simulated robots of named slots (sim_slots.hpp): the handle checks every argument before anything is enqueued
+extern "C" int pddp_simulate_problems(pddp_handle h, int count, const int* idx, const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us,
+                                      const int* substeps, const void* goal_xyz, void* xActual_inout, double* avg_err, int* failed, int family) {
+    IMPL(h); return s->simulate_problems(count, idx, x, u, KT, t0_us, elapsed_us, substeps, goal_xyz, xActual_inout, avg_err, failed, family);
+}
 extern "C" int pddp_ee_pos(pddp_handle h, int count, const void* x, void* eePos) { IMPL(h); if (!x || !eePos) return fail(PDDP_EINVAL, "null argument"); return s->ee_pos(count, x, eePos); }
 extern "C" int pddp_set_ee_cost_shift(pddp_handle h, int on) { IMPL(h); s->cfg.ee_cost_shift = on ? 1 : 0; return 0; }
 extern "C" int pddp_set_cost_ee(pddp_handle h, double Q_EE1, double Q_EE2, double QF_EE1, double QF_EE2, double R_EE, double Q_xEE, double QF_xEE,

@@ -109,6 +109,14 @@ struct PlantSimBatchOut {         // state | error | failed
     double out[2];                // average tracking error, failed flag: what plant_sim_body writes through PlantSimArgs::out
 };
 
+// the record of one entry of pddp_simulate_problems (sim_slots.hpp): the batched record, and what that call takes per launch -- the slot whose plan the entry follows,
+// its sub-step count, and the knot spacing of the slot's own horizon time in microseconds (filled on the host: the kernels read no step table)
+template <typename PD, typename T>
+struct PlantSimSlotIn : PlantSimBatchIn<PD, T> {
+    int slot, substeps;
+    double step_us;
+};
+
 // x / u / KT: THIS problem's plan, already resolved by the caller -- a slice of the uploaded plans, or the solution the handle holds (read only either way)
 template <typename PD, int INTEG, typename T>
 PDDP_HD void plant_sim_batch_body(const Wave& w, PlantSimScratch<PD, T>& s, const void* model, const PlantSimBatchIn<PD, T>& in, PlantSimBatchOut<PD, T>& out,

@@ -67,6 +67,9 @@ struct SolverBase {
                          double* avg_err, int* failed) = 0;
     virtual int simulate_batch(const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us, int substeps, const void* goal,
                                void* xActual, double* avg_err, int* failed) = 0;
+    // the simulated robots of named slots (sim_slots.hpp); checked by the handle
+    virtual int simulate_problems(int count, const int* idx, const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us,
+                                  const int* substeps, const void* goal, void* xActual, double* avg_err, int* failed, int family) = 0;
     virtual int ee_pos(int count, const void* x, void* out) = 0;
     virtual int set_cost(double Q1, double Q2, double R, double QF1, double QF2) = 0;
     virtual int set_cost_ee(const double* v) = 0;

@@ -10,6 +10,7 @@
 #include "goal_traj_table.hpp"
 #include "goal_path_table.hpp"
 #include "horizon_time_table.hpp"
+#include "sim_slots.hpp"
 #include "mpc_slots.hpp"
 #include "mpc_record.hpp"
 #include "tl_launch.hpp"
@@ -1547,7 +1548,7 @@ struct Solver : SolverBase {
         const size_t B = cfg.batch, N = cfg.N;
         if (b.dtab)                                                  // (the kernel interpolates every plan with ONE knot spacing, step_us: a refusal, not a silently wrong interpolation)
             return fail(PDDP_EINVAL, "pddp_simulate_batch: this handle has per-problem horizon times (pddp_set_horizon_time_problems), and the batched simulator takes one knot "
-                                     "spacing for the whole launch; simulate such problems with pddp_simulate on a handle of their own horizon time");
+                                     "spacing for the whole launch; pddp_simulate_problems simulates every named slot at the spacing of its own horizon time");
         if ((x != nullptr) != (u != nullptr) || (x != nullptr) != (KT != nullptr))
             return fail(PDDP_EINVAL, "pddp_simulate_batch: x, u and KT are either all given (host plans) or all NULL (the solution the handle holds)");
         if (substeps < 1) return fail(PDDP_EINVAL, "pddp_simulate_batch: substeps >= 1");
@@ -1582,6 +1583,64 @@ struct Solver : SolverBase {
         HIPCHK(hipStreamSynchronize(stream));
         const Out* hout = reinterpret_cast<const Out*>(h_simb + in_bytes);
         for (size_t i = 0; i < B; i++) {
+            std::memcpy((T*)xActual + i * NX, hout[i].x, NX * sizeof(T));
+            if (avg_err) avg_err[i] = hout[i].out[0];
+            if (failed) failed[i] = (int)hout[i].out[1];
+        }
+        return 0;
+    }
+    // pddp_simulate_problems (sim_slots.hpp): entry i is the simulated robot of slot idx[i] -- on the solution that slot holds, or on entry i of the uploaded plans --
+    // with the knot spacing of the slot's own horizon time (the host mirror ht_host where the handle has a step table, cfg.total_time otherwise) and its own sub-step
+    // count, both in the entry's record.  Slots are only read; an index may stand in many entries.  The same traffic as pddp_simulate_batch, sized by `count`: one
+    // transfer up (+ the three plans when they come from the host), one launch -- a wavefront per entry, or a thread per entry on the closed-form plants --, one
+    // transfer back, one synchronisation.  Buffers of its own, grow-only, released with the handle.
+    DeviceBuf d_simp_buf;            // device: input records, then output records
+    DeviceBuf d_simp_plan_buf;       // device: uploaded plans x | u | KT
+    PinnedBuf h_simp_buf;            // pinned: the same two record areas
+    int simulate_problems(int count, const int* idx, const void* x, const void* u, const void* KT, const double* t0_us, const double* elapsed_us, const int* substeps,
+                          const void* goal, void* xActual, double* avg_err, int* failed, int family) override {
+        using In = PlantSimSlotIn<PD, T>; using Out = PlantSimBatchOut<PD, T>;
+        const std::string complaint = sim_slots_complaint(count, idx, x, u, KT, t0_us, elapsed_us, substeps, xActual, family, P::PLANT, cfg.batch, loaded);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_simulate_problems: " + complaint);
+        const int fam = sim_slots_family(family, P::PLANT, sizeof(T) == 8, count);
+        if (int mrc = ensure_model_d()) return mrc;
+        const size_t C = (size_t)count, N = cfg.N;
+        const SimSlotsLayout lay = sim_slots_layout(C, sizeof(In), sizeof(Out));
+        if (int rc = reserve(d_simp_buf, lay.rec_bytes, "pddp_simulate_problems: hipMalloc failed for the per-entry records")) return rc;
+        if (int rc = reserve(h_simp_buf, lay.rec_bytes, "pddp_simulate_problems: hipHostMalloc failed for the per-entry records")) return rc;
+        unsigned char* const d_rec = d_simp_buf.as<unsigned char>(); unsigned char* const h_rec = h_simp_buf.as<unsigned char>();
+        const size_t nx = C * N * NX, nu = C * N * NU, nk = C * N * NX * NU;
+        const T *px = nullptr, *pu = nullptr, *pKT = nullptr;
+        if (x) {
+            if (int rc = reserve(d_simp_plan_buf, (nx + nu + nk) * sizeof(T), "pddp_simulate_problems: hipMalloc failed for the uploaded plans")) return rc;
+            T* const d_plan = d_simp_plan_buf.as<T>();
+            px = d_plan; pu = px + nx; pKT = pu + nu;
+            HIPCHK(hipMemcpyAsync(d_plan, x, nx * sizeof(T), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_plan + nx, u, nu * sizeof(T), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_plan + nx + nu, KT, nk * sizeof(T), hipMemcpyHostToDevice, stream));
+        }
+        const bool tab = b.dtab != nullptr;
+        const double handle_step_us = step_us(cfg);
+        sim_slots_fill<In, T>(reinterpret_cast<In*>(h_rec), count, idx, t0_us, elapsed_us, substeps, (const T*)goal, (const T*)xActual, NX,
+                              [&](int q) { return tab ? step_us(ht_host[(size_t)q], cfg.N) : handle_step_us; });
+        HIPCHK(hipMemcpyAsync(d_rec, h_rec, C * sizeof(In), hipMemcpyHostToDevice, stream));
+        const In* din = reinterpret_cast<const In*>(d_rec); Out* dout = reinterpret_cast<Out*>(d_rec + lay.in_bytes);
+        bool launched = false;
+        if constexpr (kDiagCost) {
+            if (fam == kSimFamilyThread) {
+                hipLaunchKernelGGL((k_plant_sim_ts<PD, INTEG, T>), dim3((unsigned)((C + 63) / 64)), dim3(64), 0, stream, model_d, din, dout, px, pu, pKT, b, (int)N, cfg.batch, count,
+                                   goal ? 1 : 0, cfg.ee_on_link_z);
+                launched = true;
+            }
+        }
+        if (!launched)
+            hipLaunchKernelGGL((k_plant_sim_slots<PD, INTEG, T>), dim3((unsigned)C), dim3(64), 0, stream, model_d, din, dout, px, pu, pKT, b, (int)N, cfg.batch, goal ? 1 : 0,
+                               cfg.ee_on_link_z);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_rec + lay.in_bytes, d_rec + lay.in_bytes, C * sizeof(Out), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        const Out* hout = reinterpret_cast<const Out*>(h_rec + lay.in_bytes);
+        for (size_t i = 0; i < C; i++) {
             std::memcpy((T*)xActual + i * NX, hout[i].x, NX * sizeof(T));
             if (avg_err) avg_err[i] = hout[i].out[0];
             if (failed) failed[i] = (int)hout[i].out[1];

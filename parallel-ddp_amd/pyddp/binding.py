@@ -574,6 +574,29 @@ class Solver:
         self._chk(self.lib.pddp_simulate_batch(self.h, _p(plans[0]), _p(plans[1]), _p(plans[2]), _p(t0), _p(el), int(substeps), _p(g), _p(xa), _p(err), _p(failed)))
         return xa, err, failed
 
+    def simulate_problems(self, idx, t0_us, elapsed_us, substeps, goal_xyz=None, xActual=None, x=None, u=None, KT=None, family=0):
+        """pddp_simulate_problems: the simulated robots of named slots, entry i = slot idx[i] (an index may repeat), each at the knot spacing of its own horizon time.
+        x / u / KT [count][N][...] = host plans; all three None: every entry follows the solution its slot holds on the device.  t0_us, elapsed_us, substeps
+        broadcast to [count], goal_xyz to [count][3], xActual to [count][n].  family: 0 the library's choice, 1 a wavefront per entry, 2 a thread per entry.
+        Returns (states [count][n] after elapsed_us, average tracking errors [count], failed [count])."""
+        idx = np.ascontiguousarray(np.asarray(idx, np.int32).ravel())
+        count = int(idx.size)
+        if xActual is None:
+            raise PddpError("pddp_simulate_problems: xActual (the measured states [count][n]) is required")
+        plans = [None if a is None else self.arr(a) for a in (x, u, KT)]
+        for a, per in zip(plans, (self.n, self.m, self.n * self.m)):
+            assert a is None or a.size == count * self.cfg.N * per
+        xa = np.array(np.broadcast_to(self.arr(xActual), (count, self.n)), dtype=self.dtype, order="C")
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0_us, np.float64), (count,)))
+        el = np.ascontiguousarray(np.broadcast_to(np.asarray(elapsed_us, np.float64), (count,)))
+        sub = np.ascontiguousarray(np.broadcast_to(np.asarray(substeps, np.int32), (count,)))
+        g = None if goal_xyz is None else np.ascontiguousarray(np.broadcast_to(self.arr(goal_xyz), (count, 3)))
+        err, failed = np.zeros(count, np.float64), np.zeros(count, np.int32)
+        self.lib.pddp_simulate_problems.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 11 + [C.c_int]
+        self._chk(self.lib.pddp_simulate_problems(self.h, count, _p(idx), _p(plans[0]), _p(plans[1]), _p(plans[2]), _p(t0), _p(el), _p(sub), _p(g), _p(xa), _p(err), _p(failed),
+                                                  int(family)))
+        return xa, err, failed
+
     def ee_pos(self, x):
         """pddp_ee_pos: tool point (x, y, z, roll, pitch, yaw) of states [count][n]."""
         x = self.arr(x).reshape(-1, self.n)
