@@ -383,6 +383,43 @@ int pddp_goal_path_profile(pddp_handle h, int timing, float* ms);
 int pddp_set_horizon_time_problems(pddp_handle h, int count, const int* idx, const double* total_time /* [count] seconds */);
 int pddp_get_horizon_time_problems(pddp_handle h, int count, const int* idx, double* total_time /* [count], may be NULL */,
                                    double* time_step /* [count], may be NULL: the step as the kernels see it, widened */);
+/* Control references of the same plants (pendulum, cart-pole, quadrotor): the other half of the tracking cost
+ * (x - x_ref)' Q (x - x_ref) + (u - u_ref)' R (u - u_ref).  A problem of such a handle either has a control reference U[N][m] in the
+ * handle's element type, or it has none.
+ *   with a reference: every place where the cost, its gradient or the initial cost of a RUNNING knot k < N-1 reads u_k in the control
+ *     term reads u_k - U[k] instead: g_k = [q .* (x_k - goal_k); r .* (u_k - U[k])], cost 1/2 (sum q_i d_i^2 + sum r_j (u_k - U[k])_j^2).
+ *     The difference is formed in the element type and squared in double, as the state's is.  k is the ABSOLUTE knot index of the
+ *     horizon, not an index inside a shooting segment.  Row N-1 is stored and returned but never read: the final knot has no control
+ *     term.  H_k, the backward pass, the linear sweeps, the line search, the control law u = ucur - alpha du - K dx and the simulators do
+ *     not change.  (The quadrotor's hover trim is 9.81 / 8 per rotor at every knot: with it a vehicle resting on its goal pays nothing,
+ *     where without it every knot pays 1/2 r sum u_j^2 and the optimum sags below the goal.)
+ *   without one: the problem behaves as it always did.
+ * Timing is that of pddp_set_goal_trajectory_problems: a reference is in force for the following loads, solves and control cycles; g and
+ * the cost of what is already in a slot are NOT rebuilt by the setter; problems that are not named keep theirs; running problems in other
+ * slots are untouched.  The first setter call gives the handle a device table [batch][N][m] in its element type and a flag per problem; a
+ * handle without a step table, a goal table and a table of diagonal cost records gets all three the way the first
+ * pddp_set_horizon_time_problems call creates them (every step the handle-wide one, no problem flagged, every cost row the built-in
+ * record); the captured sweep graph is dropped once.  Later calls only write rows and flags (on the solver's stream, one synchronisation
+ * before the call returns).  A handle that never calls the setter launches exactly the kernels and arguments it launches without these
+ * entry points.
+ * Control cycles (pddp_mpc_solve, pddp_mpc_solve_problems, pddp_mpc_load*): the library does NOT shift a control reference, as it does not
+ * shift a goal trajectory.  The rows belong to the NEW horizon's knots as they stand when the cycle starts: a hover trim is constant over
+ * the rows, a caller with a moving feed-forward writes the window with the setter before the cycle.  GOAL PATHS (above) CARRY NO CONTROL
+ * ROWS: a path windows states only.  The warm start keeps zero-filling the shifted tail of u.  pddp_load_problems,
+ * pddp_mpc_solve_problems and pddp_mpc_load_problems run the named slots with their own references; nothing is written back.
+ * pddp_get_control_reference_problems returns the stored rows and has[i] = 1 for a problem with a reference; for a problem without one
+ * (and for every problem before the first setter call) zeros and has[i] = 0.  has may be NULL.
+ * pddp_clear_control_reference_problems: the named problems pay for u itself again (from the next load / solve on, as above); on a handle
+ * that never had a table a successful no-op.
+ * PDDP_EINVAL, with the handle unchanged: plants 4 and 5; count < 1; a NULL idx or U; an index outside [0, batch); an index named twice;
+ * (setter) a value that is not finite in the handle's element type.  The handle need not be loaded yet.
+ * A first setter call whose device allocation or transfer fails (PDDP_ENOMEM / PDDP_ENODEVICE) follows the rule of
+ * pddp_set_horizon_time_problems: no reference table, but possibly the step, goal and cost tables it created first, at their defaults;
+ * the handle computes what it computed before, and the call can be repeated. */
+int pddp_control_reference_size(pddp_handle h);                                 /* N * m */
+int pddp_set_control_reference_problems(pddp_handle h, int count, const int* idx, const void* U /* [count][N][m], handle dtype */);
+int pddp_get_control_reference_problems(pddp_handle h, int count, const int* idx, void* U /* [count][N][m] */, int* has /* [count], may be NULL */);
+int pddp_clear_control_reference_problems(pddp_handle h, int count, const int* idx);
 /* ---- the lock-step experiment around the solver ------------------------- */
 /* simulateForward<T, SUBSTEPS> (examples/WAFR_MPC_examples.cu:111-139): the simulated robot of the lock-step MPC experiment.  Starting
  * from xActual at plant time t0_us (the plan's t0), integrates the plant IN DOUBLE for elapsed_us in `substeps` steps under the trajectory

@@ -284,8 +284,9 @@ struct FpCfStage {
     static constexpr int PW = 64 / A, NX = P::NX, NU = P::NU;
     union {
         struct { T M[PW][NX * NX], xp[PW][NX], Bdu[PW][NX], d[PW][NX]; } sw;
-        struct { T K[PW][NX * NU], xp[PW][NX], up[PW][NU], du[PW][NU], xg[PW][NX]; } ro;      // xg: the knot's goal, travelling with xp (a GoalTab plant only; the sweep's half of the union is the larger one)
+        struct { T K[PW][NX * NU], xp[PW][NX], up[PW][NU], du[PW][NU], xg[PW][NX], ug[PW][NU]; } ro;      // xg: the knot's goal, travelling with xp (a GoalTab plant only); ug: the knot's control reference (a RefTab plant only); the sweep's half of the union is the larger one
     };
+    static_assert(sizeof(ro) <= sizeof(sw), "the rollouts' half fits inside the sweep's: the stage keeps its size");
 };
 template <typename T, int PW, int L>
 struct FpCfRegs { static constexpr int R = (PW * L + 63) / 64; T v[R]; };
@@ -434,6 +435,17 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
         gt_on = lane < PW * NX && b.gflag[q] != 0;
         if (lane < PW * NX) { const T v = b.xGoal[(size_t)q * NX + e]; (&stage[0].ro.xg[0][0])[lane] = v; (&stage[1].ro.xg[0][0])[lane] = v; }
     }
+    // a control reference (RefTab, plants.hpp) travels the same way: the lane < PW * NU lanes fetch their element of knot k + 1's row one step ahead and write it into
+    // ro.ug.  Both stages start out at zero and only the lanes of a flagged problem store, so an unflagged problem in the same wavefront subtracts zero at every knot.
+    // The final knot has no control term: RefTab::cost does not read ug there.
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t r_ut; [[maybe_unused]] unsigned ut_off = 0; [[maybe_unused]] bool ut_on = false; [[maybe_unused]] T rug = T(0);
+    if constexpr (IsRefTab<P>::value && PART == 1) {
+        const int p = lane / NU, q = (pb0 + p < batch) ? pb0 + p : batch - 1, e = lane - p * NU;
+        r_ut = mx_rsrc(b.utab + (size_t)pb0 * N * NU);
+        ut_off = lane < PW * NU ? (unsigned)(((size_t)(q - pb0) * N * NU + e) * sizeof(T)) : 0u;      // (a lane without a share reads the block's first element and drops it)
+        ut_on = lane < PW * NU && b.uflag[q] != 0;
+        if (lane < PW * NU) { (&stage[0].ro.ug[0][0])[lane] = T(0); (&stage[1].ro.ug[0][0])[lane] = T(0); }
+    }
     const T alpha = b.alpha[a_idx];
     // the current trajectory sits in one half of xb per PROBLEM (state.cur): this lane's share of the state fetch is entry e of problem p
     const __amdgpu_buffer_rsrc_t r_xcur = mx_rsrc(b.xb + (size_t)pb0 * 2 * N * NX);
@@ -509,12 +521,14 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
         fp_cf_fetch<T, PW, NU>(rup, lU, r_up, k);
         fp_cf_fetch<T, PW, NU>(rdu, lU, r_du, k);
         if constexpr (IsGoalTab<P>::value) rxg = mx_bld<T>(r_gt, gt_off, (unsigned)k * (unsigned)(NX * sizeof(T)));
+        if constexpr (IsRefTab<P>::value) rug = mx_bld<T>(r_ut, ut_off, (unsigned)k * (unsigned)(NU * sizeof(T)));
     };
     auto put = [&](FpCfStage<P, T, A>& sg) {
         fp_cf_put<T, PW, NX * NU>(rK, &sg.ro.K[0][0], lane);
         if (xlane) (&sg.ro.xp[0][0])[lane] = rxp;
         fp_cf_put<T, PW, NU>(rup, &sg.ro.up[0][0], lane); fp_cf_put<T, PW, NU>(rdu, &sg.ro.du[0][0], lane);
         if constexpr (IsGoalTab<P>::value) { if (gt_on) (&sg.ro.xg[0][0])[lane] = rxg; }
+        if constexpr (IsRefTab<P>::value) { if (ut_on) (&sg.ro.ug[0][0])[lane] = rug; }
     };
     fetch(0); put(stage[0]); wsync();
     // a step table (StepTab, plants.hpp): this lane's problem's own step, ONE load in front of the step loop into the register the scalar argument would occupy -- a load
@@ -538,7 +552,8 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
             uv -= alpha * sc.ro.du[grp][r] + Kdx;
             u[r] = uv;
         }
-        if constexpr (IsGoalTab<P>::value) cost_k[k] = P::cost(cw, x, u, sc.ro.xg[grp], k, N);      // knot k's goal, from the stage
+        if constexpr (IsRefTab<P>::value) cost_k[k] = P::cost(cw, x, u, KnotRef<T>{sc.ro.xg[grp], sc.ro.ug[grp]}, k, N);      // knot k's goal and control reference, from the stage
+        else if constexpr (IsGoalTab<P>::value) cost_k[k] = P::cost(cw, x, u, sc.ro.xg[grp], k, N);      // knot k's goal, from the stage
         else cost_k[k] = P::cost(cw, x, u, xg, k, N);
         cf_integrator_step<P, INTEG, T>(xn, x, u, dtl);
         put(stage[(k + 1) & 1]); wsync();
@@ -562,7 +577,8 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
         PDDP_UNROLL for (int i = 0; i < NX; i++) rec[i] = x[i];
         PDDP_UNROLL for (int r = 0; r < NU; r++) rec[NX + r] = u[r];
         if (live) cf_bst_vec<T, REC>(r_rec, rec_off, (unsigned)(N - 1) * rstr, rec);
-        if constexpr (IsGoalTab<P>::value) cost_k[N - 1] = P::cost(cw, x, u, sc.ro.xg[grp], N - 1, N);      // (stage (N - 1) & 1 holds row N - 1)
+        if constexpr (IsRefTab<P>::value) cost_k[N - 1] = P::cost(cw, x, u, KnotRef<T>{sc.ro.xg[grp], sc.ro.ug[grp]}, N - 1, N);
+        else if constexpr (IsGoalTab<P>::value) cost_k[N - 1] = P::cost(cw, x, u, sc.ro.xg[grp], N - 1, N);      // (stage (N - 1) & 1 holds row N - 1)
         else cost_k[N - 1] = P::cost(cw, x, u, xg, N - 1, N);
         dmx = tmax(dmx, T(0));
     }
@@ -663,6 +679,7 @@ template <typename T> struct GradZeroCols<QuadPlant<T>> { static constexpr unsig
 template <typename B, typename T> struct GradZeroCols<DiagTab<B, T>> : GradZeroCols<B> {};                               // (the same dynamics)
 template <typename B, typename T> struct GradZeroCols<GoalTab<B, T>> : GradZeroCols<B> {};
 template <typename B, typename T> struct GradZeroCols<StepTab<B, T>> : GradZeroCols<B> {};
+template <typename B, typename T> struct GradZeroCols<RefTab<B, T>> : GradZeroCols<B> {};
 template <typename P> struct GradCols {
     static constexpr int NM = P::NX + P::NU;
     static constexpr unsigned zero = GradZeroCols<P>::value;
@@ -714,13 +731,20 @@ __global__ __launch_bounds__(64) void k_nis_kb(Buffers<T> b, Dims dm, CostWeight
                 }
                 if (mode == 1 || !st.done) {
                     if (do_g) {
-                        const T* xg = goal_at(problem_goal<P, T>(b, pb, N), k);      // (a goal trajectory: the row of (pb, k))
+                        const auto kg = goal_at(problem_goal<P, T>(b, pb, N), k);      // (a goal trajectory: the row of (pb, k); a control reference: its row of (pb, k) beside it)
+                        const T* xg = goal_row(kg);
                         T* gk = b.g + ((size_t)pb * N + k) * NM;
                         if constexpr (P::kPluginCost) P::cost_grad(cw, b.H + ((size_t)pb * N + k) * NM * NM, gk, x, u, xg, k, N);
                         else {
                             T gv[NM], xgv[NX];
                             cf_load_vec<T, NX>(xgv, xg);
-                            PDDP_UNROLL for (int i = 0; i < NM; i++) gv[i] = knot_weight<P, T>(b, cw, pb, i, k, N) * (i < NX ? (x[i] - xgv[i]) : u[i - NX]);
+                            if constexpr (IsRefTab<P>::value) {                 // u - U[k]: the lane reads its (pb, k) row once (the quadrotor's: one 16-byte load); the final knot has no control term
+                                T urv[NU];
+                                cf_load_vec<T, NU>(urv, kg.ur);
+                                PDDP_UNROLL for (int i = 0; i < NM; i++) gv[i] = knot_weight<P, T>(b, cw, pb, i, k, N) * (i < NX ? (x[i] - xgv[i]) : (k == N - 1 ? u[i - NX] : u[i - NX] - urv[i - NX]));
+                            } else {
+                                PDDP_UNROLL for (int i = 0; i < NM; i++) gv[i] = knot_weight<P, T>(b, cw, pb, i, k, N) * (i < NX ? (x[i] - xgv[i]) : u[i - NX]);
+                            }
                             cf_store_vec<T, NM>(gk, gv);
                         }
                     }

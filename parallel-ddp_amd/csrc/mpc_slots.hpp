@@ -6,7 +6,7 @@
 // tables, one launch each.
 //   in and out   the solver state, derivatives ([A B] in both layouts where the compact one exists), sweep operands, candidates (and their knot-major records / segment
 //                maps where the family keeps them), line-search inputs, observables
-//   in only      what a cycle reads and never writes: xTarget, the slot's row of the cost table, its goal trajectory and flag, its time step
+//   in only      what a cycle reads and never writes: xTarget, the slot's row of the cost table, its goal trajectory and flag, its time step, its control reference and flag
 //   out only     what the load stage writes whole before anything reads it: du, dmax, err, the fall-back copies, xGoal, tshift; the cycle's inputs as the arrays
 //                "xActual" / "shift" / "mpc_in" show them after a whole-handle call; and the previous solution the load stage shifts -- both halves of xb, u, d, the
 //                cost-to-go double buffer, the gains --, which does not go in through the movers at all: k_mpc_load_slots (kernels.hpp) reads it from the slot while
@@ -28,6 +28,7 @@ struct MpcSlotSide {                 // one side (handle or intake area) of the 
     T *xActual, *goal_in; int* shift;      // the three runs of "mpc_in"
     T* gtab; int* gflag;             // the goal trajectories [.][N][NX] and their flags, or null (both sides or neither)
     T* dtab = nullptr;               // the per-problem time steps [.], or null (both sides or neither)
+    T* utab = nullptr; int* uflag = nullptr;      // the control references [.][N][NU] (row 0 of problem 0: behind the side's own zero row) and their flags, or null (both sides or neither)
 };
 
 template <int NX, int NU, typename T>
@@ -66,6 +67,7 @@ bool mpc_slot_tables(std::vector<SlotTable>& in_t, std::vector<SlotTable>& out_t
     if (hs.cwt_rows) add(1, is.cwt_rows, hs.cwt_rows, (cwt_rec ? cwt_rec : cost_record_len(ee_cost)) * e);
     if (hs.gtab) { add(1, is.gtab, hs.gtab, N * NX * e); add(1, is.gflag, hs.gflag, sizeof(int)); }      // in only: a cycle does not change a trajectory
     if (hs.dtab) add(1, is.dtab, hs.dtab, e);                                                            // in only: nor its slot's time step
+    if (hs.utab) { add(1, is.utab, hs.utab, N * NU * e); add(1, is.uflag, hs.uflag, sizeof(int)); }      // in only: nor its control reference
     add(2, is.xActual, hs.xActual, NX * e); add(2, is.goal_in, hs.goal_in, NX * e); add(2, is.shift, hs.shift, sizeof(int));
     return ok;
 }

@@ -23,8 +23,9 @@ struct NisScratch {
 };
 
 // xk/uk: the knot's state and control (global).  Writes ABk (k < N-1), Hk, gk (global).
-template <typename P, int INTEG, typename T, typename CW = CostWeights<T>>      // CW: the record as the plant's cost routines take it (plants.hpp DiagCostWeights for a DiagTab plant)
-PDDP_HD void nis_knot(const Wave& w, NisScratch<P, INTEG, T>& s, const Dims& dm, int k, const T* xk, const T* uk, const T* xg,
+// G: the knot's goal as goal_at (plants.hpp) gives it -- a pointer, or on a RefTab plant the knot's goal row and control reference row
+template <typename P, int INTEG, typename T, typename CW = CostWeights<T>, typename G = const T*>      // CW: the record as the plant's cost routines take it (plants.hpp DiagCostWeights for a DiagTab plant)
+PDDP_HD void nis_knot(const Wave& w, NisScratch<P, INTEG, T>& s, const Dims& dm, int k, const T* xk, const T* uk, const G& xg,
                       const CW& cw, T dt, T* ABk, T* Hk, T* gk, const T* xt = nullptr, int tshift = 0, T* cost_out = nullptr, bool write_const_H = true) {
     constexpr int NX = P::NX, NU = P::NU, NM = NX + NU;
     PDDP_FOR(i, NX) s.x[i] = xk[i];
@@ -52,7 +53,7 @@ PDDP_HD void nis_knot(const Wave& w, NisScratch<P, INTEG, T>& s, const Dims& dm,
     // kernels have always done so)
     if (write_const_H) PDDP_FOR(e, NM * NM) { const int i = e / NM, j = e % NM; Hk[e] = (i == j) ? P::weight(cw, i, k, dm.N) : T(0); }
     PDDP_FOR(i, NM) {
-        T gv = P::weight(cw, i, k, dm.N) * (i < NX ? (s.x[i] - xg[i]) : s.u[i - NX]);
+        T gv = P::weight(cw, i, k, dm.N) * (i < NX ? (s.x[i] - goal_row(xg)[i]) : control_term(xg, s.u, i - NX, k == dm.N - 1));      // (a control reference: u - U[k], plants.hpp)
         if constexpr (P::PLANT == 4) { if (cw.limits && (k < dm.N - 1 || i < NX)) gv += arm_limit_term<T>(s.x, s.u, i, 1); }      // USE_LIMITS_FLAG: the gradient only, H stays (cost_arm.cuh:176-199)
         gk[i] = gv;
     }

@@ -145,6 +145,15 @@ extern "C" int pddp_set_horizon_time_problems(pddp_handle h, int count, const in
 extern "C" int pddp_get_horizon_time_problems(pddp_handle h, int count, const int* idx, double* total_time, double* time_step) {
     IMPL(h); return s->get_horizon_time_problems(count, idx, total_time, time_step);
 }
+// control references of the same plants (control_ref_table.hpp): the handle checks every argument before it is touched
+extern "C" int pddp_control_reference_size(pddp_handle h) {
+    IMPL(h);
+    const int len = s->control_reference_size();
+    return len ? len : fail(PDDP_EINVAL, "pddp_control_reference_size: control references belong to the pendulum, cart-pole and quadrotor (plants 1-3)");
+}
+extern "C" int pddp_set_control_reference_problems(pddp_handle h, int count, const int* idx, const void* U) { IMPL(h); return s->set_control_reference_problems(count, idx, U); }
+extern "C" int pddp_get_control_reference_problems(pddp_handle h, int count, const int* idx, void* U, int* has) { IMPL(h); return s->get_control_reference_problems(count, idx, U, has); }
+extern "C" int pddp_clear_control_reference_problems(pddp_handle h, int count, const int* idx) { IMPL(h); return s->clear_control_reference_problems(count, idx); }
 // goal paths of the same plants (goal_path_table.hpp): the handle checks every argument before it is touched
 extern "C" int pddp_reserve_goal_path(pddp_handle h, int capacity) { IMPL(h); return s->reserve_goal_path(capacity); }
 extern "C" int pddp_goal_path_capacity(pddp_handle h) { IMPL(h); return s->goal_path_capacity(); }

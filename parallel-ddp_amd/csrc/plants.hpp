@@ -290,9 +290,22 @@ template <typename T>
 struct GoalRows { const T* base; int stride; };
 template <typename T> PDDP_HD const T* goal_at(const T* g, int) { return g; }
 template <typename T> PDDP_HD const T* goal_at(const GoalRows<T>& g, int k) { return g.base + (size_t)k * g.stride; }      // k: the ABSOLUTE knot of the horizon
+// (RefTab, the top layer below: the knot's control reference travels beside the knot's goal)
+template <typename T>
+struct KnotRef { const T* xg; const T* ur; };
+template <typename T>
+struct RefRows { const T* base; int stride; const T* ubase; int ustride; };
+template <typename T> PDDP_HD KnotRef<T> goal_at(const RefRows<T>& g, int k) { return KnotRef<T>{g.base + (size_t)k * g.stride, g.ubase + (size_t)k * g.ustride}; }      // k: the ABSOLUTE knot of the horizon
+template <typename B, typename T> struct RefTab;
+template <typename P> struct IsRefTab { static constexpr bool value = false; };
+template <typename B, typename T> struct IsRefTab<RefTab<B, T>> { static constexpr bool value = true; };
 template <typename P, typename T>
 PDDP_HD auto problem_goal(const Buffers<T>& b, int pb, int N) {
-    if constexpr (IsGoalTab<P>::value) {
+    if constexpr (IsRefTab<P>::value) {                             // (control references, below: the goal's base and stride and the reference's)
+        const bool on = b.gflag[pb] != 0, uon = b.uflag[pb] != 0;
+        return RefRows<T>{on ? b.gtab + (size_t)pb * N * P::NX : b.xGoal + (size_t)pb * P::NX, on ? P::NX : 0,
+                          uon ? b.utab + (size_t)pb * N * P::NU : b.utab - control_ref_pad<T>(P::NU), uon ? P::NU : 0};
+    } else if constexpr (IsGoalTab<P>::value) {
         const bool on = b.gflag[pb] != 0;
         return GoalRows<T>{on ? b.gtab + (size_t)pb * N * P::NX : b.xGoal + (size_t)pb * P::NX, on ? P::NX : 0};
     } else return (const T*)(b.xGoal + (size_t)pb * P::NX);
@@ -317,6 +330,45 @@ PDDP_HD T problem_dt(const Buffers<T>& b, int pb, T dt) {
     if constexpr (IsStepTab<P>::value) return b.dtab[pb];
     else return dt;
 }
+
+// ---- control references of the same plants (pddp_set_control_reference_problems) ----
+// Buffers::utab is null, or a table [batch][N][NU] with a flag per problem (Buffers::uflag): a flagged problem's control term of the running knot k is taken on
+// u_k - U[k], an unflagged one's on u_k as always.  RefTab<B, T> is StepTab<B, T> -- the same records, goals and steps -- for the handles that have such a table: the
+// top layer of the chain, a policy of its own, so that the instantiations below it are the ones they always were.  The knot's reference travels beside the knot's goal:
+// on RefTab problem_goal returns RefRows (goal base and stride, reference base and stride) and goal_at a KnotRef (the knot's goal row and reference row), and cost() /
+// cost_grad() take the KnotRef -- the pointer forms of the layers below are hidden, so a call that would have no reference does not compile.  Branch-free: an
+// unflagged problem reads the table's zero row with stride 0 (solver_state.hpp: control_ref_pad elements of zeros in FRONT of the table, b.utab points behind
+// them), and u - 0 is u bit for bit; a wavefront may hold problems with and without a reference.  The difference is formed in T and squared in double, as dl is.
+// Kernels that form no control term (backward passes, linear sweeps, line search, movers, simulators, warm start) have no RefTab instantiation.
+template <typename B, typename T>
+struct RefTab : StepTab<B, T> {
+    static constexpr int NX = B::NX, NU = B::NU;
+    template <typename U> using Rebind = RefTab<typename B::template Rebind<U>, U>;
+    static PDDP_HD T cost(const DiagCostWeights<T>& cw, const T* xk, const T* uk, const KnotRef<T>& ref, int k, int N) {      // DiagTab::cost on u - U[k]
+        const T* r = cw.row;
+        T cost = 0.0;
+        for (int i = 0; i < NX; i++) { const double dl = xk[i] - ref.xg[i]; cost += (k == N - 1 ? r[NX + NU + i] : r[i]) * (dl * dl); }
+        if (k != N - 1) for (int i = 0; i < NU; i++) { const double uu = uk[i] - ref.ur[i]; cost += r[NX + i] * (uu * uu); }
+        return 0.5 * cost;
+    }
+    static PDDP_HD void cost_grad(const DiagCostWeights<T>& cw, T* Hk, T* gk, const T* xk, const T* uk, const KnotRef<T>& ref, int k, int N) {      // DiagTab::cost_grad on u - U[k]
+        constexpr int NM = NX + NU;
+        const T* r = cw.row;
+        for (int i = 0; i < NM; i++) for (int j = 0; j < NM; j++) Hk[i * NM + j] = i != j ? T(0) : DiagTab<B, T>::weight_row(r, i, k, N);
+        for (int i = 0; i < NX; i++) gk[i] = (k == N - 1 ? r[NX + NU + i] : r[i]) * (xk[i] - ref.xg[i]);
+        for (int i = 0; i < NU; i++) gk[i + NX] = k == N - 1 ? T(0) * uk[i] : r[NX + i] * (uk[i] - ref.ur[i]);      // (the final knot has no control term: its row is not read)
+    }
+};
+template <typename B, typename T> struct IsDiagTab<RefTab<B, T>> { static constexpr bool value = true; };
+template <typename B, typename T> struct IsGoalTab<RefTab<B, T>> { static constexpr bool value = true; };
+template <typename B, typename T> struct IsStepTab<RefTab<B, T>> { static constexpr bool value = true; };
+// the control term's operand of index j at knot k: u_j on every other policy, u_j - U[k][j] on RefTab (nis_knot, k_nis_kb: the lanes that form g themselves)
+template <typename T> PDDP_HD const T* goal_row(const T* g) { return g; }
+template <typename T> PDDP_HD const T* goal_row(const KnotRef<T>& g) { return g.xg; }
+// (fin: the final knot, whose weight is zero and whose row is stored but never read -- the operand stays u_j there, so that the sign of the zero it leaves in g does not
+// depend on the row)
+template <typename T> PDDP_HD T control_term(const T*, const T* u, int j, bool) { return u[j]; }
+template <typename T> PDDP_HD T control_term(const KnotRef<T>& g, const T* u, int j, bool fin) { return fin ? u[j] : u[j] - g.ur[j]; }
 
 // A scalar plug-in's gradient routine also returns qdd; the kernel families build the midpoint / RK3 stage states from that qdd (serial paths) or from the dynamics routine's
 // (the staged three-lane path of integrators.hpp), so the two have to be the SAME numbers -- the reference's plug-ins call dynamics() inside dynamicsGradient.  Checked on the

@@ -90,6 +90,11 @@ struct SolverBase {
     // per-problem horizon times of the same plants (horizon_time_table.hpp); checked by the handle.  total_time / time_step may be null in the getter
     virtual int set_horizon_time_problems(int count, const int* idx, const double* total_time) = 0;
     virtual int get_horizon_time_problems(int count, const int* idx, double* total_time, double* time_step) = 0;
+    // control references of the same plants (control_ref_table.hpp); checked by the handle.  U in the handle's dtype, [count][N][NU]
+    virtual int control_reference_size() const = 0;          // N * NU numbers per problem; 0: the plant has no control references
+    virtual int set_control_reference_problems(int count, const int* idx, const void* U) = 0;
+    virtual int get_control_reference_problems(int count, const int* idx, void* U, int* has) = 0;
+    virtual int clear_control_reference_problems(int count, const int* idx) = 0;
     // goal paths of the same plants (goal_path_table.hpp): device-resident references, windowed into the goal table by every call that shifts the previous solution
     virtual int reserve_goal_path(int capacity) = 0;
     virtual int goal_path_capacity() = 0;          // rows per problem; 0 before the reserve

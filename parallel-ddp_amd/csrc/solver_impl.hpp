@@ -10,6 +10,7 @@
 #include "goal_traj_table.hpp"
 #include "goal_path_table.hpp"
 #include "horizon_time_table.hpp"
+#include "control_ref_table.hpp"
 #include "sim_slots.hpp"
 #include "mpc_slots.hpp"
 #include "mpc_record.hpp"
@@ -259,7 +260,7 @@ struct Solver : SolverBase {
     // what starts a solve from the loaded trajectory: initial cost, setup kernel in init mode and, for the end-effector cost, the cost's second pass (its initial cost comes
     // out of the setup kernel).  keep_alpha: the MPC call keeps alphaIndex (runiLQR_MPC_GPU does not reset it)
     void launch_init_cost(hipStream_t s, int ignore_first_defect, int rollout, int stage, int keep_alpha) {
-        with_cost_plant([&](auto pl) {
+        with_ref_cost_plant([&](auto pl) {
             using Q = decltype(pl);
             hipLaunchKernelGGL((k_init_cost<Q, T>), dim3(cfg.batch), dim3(64), (size_t)cfg.N * sizeof(T), s, b, dm, cw, sp, ignore_first_defect, rollout, stage, keep_alpha);
         });
@@ -283,7 +284,7 @@ struct Solver : SolverBase {
         if constexpr (P::PLANT != 4 && P::kScalarPlugin && (64 / AA) * P::NX <= 64) {
             const unsigned B = cfg.batch;
             const dim3 grid((B + 64 / AA - 1) / (64 / AA));
-            if (rollouts) with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B); });
+            if (rollouts) with_ref_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B); });
             else hipLaunchKernelGGL((k_sweep_cf<P, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B);
         }
     }
@@ -332,10 +333,10 @@ struct Solver : SolverBase {
             break;
         case kFpKernCf: if (cfg.A == 16) launch_cf<16>(s, true); else if (cfg.A == 8) launch_cf<8>(s, true); break;
         case kFpKernTs:           // (the arm has its own families: no thread-serial instantiation of its cooperative bodies)
-            if constexpr (P::PLANT != 4) with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, L.seed == 2 ? 1 : 0); });
+            if constexpr (P::PLANT != 4) with_ref_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, L.seed == 2 ? 1 : 0); });
             break;
         case kFpKernCoop:
-            with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(A_all, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, L.seed); });
+            with_ref_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(A_all, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, L.seed); });
             break;
         }
         if constexpr (P::PLANT != 4) { if (L.cand_to_xw && b.xw) hipLaunchKernelGGL((k_cand_to_xw<P, T>), dim3((unsigned)(((size_t)B * cfg.N * cfg.A + 255) / 256)), dim3(256), 0, s, b, dm, (int)B); }
@@ -365,12 +366,12 @@ struct Solver : SolverBase {
             }
             break;
         case kNisTs:
-            if constexpr (P::PLANT != 4) with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis_ts<Q, INTEG, T>), dim3((B * cfg.N + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); });
+            if constexpr (P::PLANT != 4) with_ref_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis_ts<Q, INTEG, T>), dim3((B * cfg.N + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B); });
             break;
         case kNisKb:
             if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16 && INTEG == 3 && P::kScalarPlugin) {
                 const int units = (int)(B * cfg.N);
-                with_step_plant([&](auto pl) {
+                with_ref_plant([&](auto pl) {
                     using Q = decltype(pl);
                     if (plan.kb_nis == 16) hipLaunchKernelGGL((k_nis_kb<Q, T, 16>), dim3((units + 15) / 16), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
                     else if (plan.kb_nis == 20) hipLaunchKernelGGL((k_nis_kb<Q, T, 20>), dim3((units + 19) / 20), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
@@ -381,7 +382,7 @@ struct Solver : SolverBase {
             break;
         case kNisGl:
             if constexpr (P::PLANT != 4 && P::NX + P::NU <= 16) {
-                with_step_plant([&](auto pl) {
+                with_ref_plant([&](auto pl) {
                     using Q = decltype(pl);
                     if (plan.gl_nis8) hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 8>), dim3((B * cfg.N + 7) / 8), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
                     else hipLaunchKernelGGL((k_nis_gl<Q, INTEG, T, 16>), dim3((B * cfg.N + 3) / 4), dim3(64), 0, s, b, dm, cw, dt, mode, (int)B);
@@ -390,7 +391,7 @@ struct Solver : SolverBase {
             break;
         case kNisCoop:
             if constexpr (P::PLANT == 4) { if (b.cwt) { hipLaunchKernelGGL((k_nis<P, INTEG, T, true>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); break; } }
-            with_step_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis<Q, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); });
+            with_ref_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_nis<Q, INTEG, T>), dim3(cfg.N, B), dim3(64), 0, s, b, dm, cw, dt, mode); });
             break;
         }
     }
@@ -670,6 +671,16 @@ struct Solver : SolverBase {
         if constexpr (kDiagCost) { if (b.dtab) { f(StepTab<P, T>{}); return; } }
         with_cost_plant(f);
     }
+    // the kernels that form the control term of the cost (rollouts, setup): RefTab<P, T> for a handle with a table of control references (it always has the other
+    // three tables), with_step_plant's choice otherwise; with_ref_cost_plant: the same for the initial cost, which integrates nothing and falls through to with_cost_plant
+    template <typename F> void with_ref_plant(F&& f) {
+        if constexpr (kDiagCost) { if (b.utab) { f(RefTab<P, T>{}); return; } }
+        with_step_plant(f);
+    }
+    template <typename F> void with_ref_cost_plant(F&& f) {
+        if constexpr (kDiagCost) { if (b.utab) { f(RefTab<P, T>{}); return; } }
+        with_cost_plant(f);
+    }
     int diag_refuse(const char* who) { return fail(PDDP_EINVAL, std::string(who) + ": diagonal cost records belong to the pendulum, cart-pole and quadrotor (plants 1-3); the arm has pddp_set_cost_problems, a plug-in plant its own cost file"); }
     // first setter call: the table, every row the built-in record; b.cwt; the captured graph goes once (other kernels, another argument)
     int ensure_diag_table() {
@@ -873,6 +884,100 @@ struct Solver : SolverBase {
             if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string("pddp_get_horizon_time_problems: transfer failed: ") + hipGetErrorString(e != hipSuccess ? e : es));
         }
         for (int i = 0; i < count; i++) step[i] = (double)ht_stage[i];
+        return 0;
+    }
+    // ---- control references of the same plants (control_ref_table.hpp, plants.hpp RefTab): pddp_set_control_reference_problems / pddp_get_... / pddp_clear_...
+    // A table [batch][N][NU] behind its zero row and a flag per problem, from the first setter call on; b.utab / b.uflag are what the kernels see.  With them every kernel
+    // that forms the control term of the cost or of its gradient runs in its RefTab instantiation (with_ref_plant, with_ref_cost_plant); a flagged problem's running knot k
+    // reads row k of its block, an unflagged one the zero row.  A handle with a reference table always has the step, goal and cost tables too (RefTab is layered on
+    // StepTab), created through ensure_step_table: default entries, no problem flagged, the built-in rows.
+    DeviceBuf d_utab, d_uflag;
+    T* utab_rows() const { return d_utab.template as<T>() + control_ref_pad<T>(NU); }      // (behind the zero row)
+    int* uflag_rows() const { return d_uflag.template as<int>(); }
+    std::vector<int> uf_stage;                     // host flags of the call in flight
+    size_t ref_len() const { return (size_t)cfg.N * NU; }
+    int control_reference_size() const override { return kDiagCost ? (int)ref_len() : 0; }
+    int ref_refuse(const char* who) { return fail(PDDP_EINVAL, std::string(who) + ": control references belong to the pendulum, cart-pole and quadrotor (plants 1-3)"); }
+    // room for `rows` problems: the zero row, the blocks and the flags all cleared; the kernels do not see it yet
+    int reserve_ref_table(int rows) {
+        const size_t bytes = control_ref_table_elems<T>(rows, cfg.N, NU) * sizeof(T);
+        if (int rc = reserve(d_utab, bytes, "hipMalloc failed for the control references")) return rc;
+        if (int rc = reserve(d_uflag, (size_t)rows * sizeof(int), "hipMalloc failed for the control references' flags")) return rc;
+        hipError_t e = hipMemsetAsync(d_utab.ptr, 0, bytes, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_uflag.ptr, 0, (size_t)rows * sizeof(int), stream);
+        return e == hipSuccess ? 0 : fail(PDDP_ENODEVICE, std::string("control references: clearing the table failed: ") + hipGetErrorString(e));
+    }
+    // first setter call: the step, goal and cost tables if there are none, the reference table, no problem flagged; b.utab / b.uflag; the captured graph goes once (other
+    // kernels).  Everything of the reference table is released again if a step fails; what ensure_step_table() created before that step stays, by the rule written there: a
+    // failed allocation or transfer here (PDDP_ENOMEM / PDDP_ENODEVICE) leaves the handle with the tables of a first pddp_set_horizon_time_problems call at their defaults,
+    // which compute what it computed without them, and with no reference table; the call can be repeated.
+    int ensure_ref_table() {
+        if (b.utab) return 0;
+        if constexpr (kDiagCost) {
+            if (int rc = ensure_step_table()) return rc;
+            if (int rc = reserve_ref_table(cfg.batch)) { d_utab.release(); d_uflag.release(); return rc; }
+            hipError_t e = hipStreamSynchronize(stream);            // (nothing in flight reads the old argument set)
+            if (e == hipSuccess && fp_lds > 48 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fp<RefTab<P, T>, INTEG, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp_lds);
+            if (e != hipSuccess) { d_utab.release(); d_uflag.release(); return fail(PDDP_ENODEVICE, std::string("control references: creating the table failed: ") + hipGetErrorString(e)); }
+            b.utab = utab_rows(); b.uflag = uflag_rows();
+            drop_graph();
+        }
+        return 0;
+    }
+    // flag `on` for the named problems, on the stream (uf_stage stays alive until the caller has waited for it)
+    int ref_flags_upload(int count, const int* idx, int on) {
+        uf_stage.assign((size_t)count, on);
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int len) {
+            if (e == hipSuccess) e = hipMemcpyAsync(uflag_rows() + idx[first], uf_stage.data() + first, (size_t)len * sizeof(int), hipMemcpyHostToDevice, stream);
+        });
+        return e == hipSuccess ? 0 : fail(PDDP_ENODEVICE, std::string("control references: transfer of flags failed: ") + hipGetErrorString(e));
+    }
+    int set_control_reference_problems(int count, const int* idx, const void* Uv) override {
+        if (!kDiagCost) return ref_refuse("pddp_set_control_reference_problems");
+        const T* U = static_cast<const T*>(Uv);
+        const std::string complaint = control_rows_complaint<T>(count, idx, U, cfg.batch, cfg.N, NU);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_control_reference_problems: " + complaint);
+        if (int rc = ensure_ref_table()) return rc;
+        const size_t len = ref_len();
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int run) {     // contiguous runs of slots in one transfer each; problems that are not named keep theirs
+            if (e == hipSuccess) e = hipMemcpyAsync(utab_rows() + (size_t)idx[first] * len, U + (size_t)first * len, (size_t)run * len * sizeof(T), hipMemcpyHostToDevice, stream);
+        });
+        if (e != hipSuccess) { hipStreamSynchronize(stream); return fail(PDDP_ENODEVICE, std::string("pddp_set_control_reference_problems: transfer of rows failed: ") + hipGetErrorString(e)); }
+        const int rc = ref_flags_upload(count, idx, 1);
+        HIPCHK(hipStreamSynchronize(stream));
+        return rc;
+    }
+    int clear_control_reference_problems(int count, const int* idx) override {
+        if (!kDiagCost) return ref_refuse("pddp_clear_control_reference_problems");
+        const std::string complaint = control_rows_complaint<T>(count, idx, nullptr, cfg.batch, cfg.N, NU, false);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_clear_control_reference_problems: " + complaint);
+        if (!b.utab) return 0;                                      // never had a reference: every control term is taken on u already
+        const int rc = ref_flags_upload(count, idx, 0);
+        HIPCHK(hipStreamSynchronize(stream));
+        return rc;
+    }
+    int get_control_reference_problems(int count, const int* idx, void* Uv, int* has) override {
+        if (!kDiagCost) return ref_refuse("pddp_get_control_reference_problems");
+        T* U = static_cast<T*>(Uv);
+        const std::string complaint = control_rows_complaint<T>(count, idx, U, cfg.batch, cfg.N, NU, true, false);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_get_control_reference_problems: " + complaint);
+        const size_t len = ref_len();
+        uf_stage.assign((size_t)count, 0);
+        if (b.utab) {
+            hipError_t e = hipSuccess;
+            for_each_slot_run(count, idx, [&](int first, int run) {
+                if (e == hipSuccess) e = hipMemcpyAsync(U + (size_t)first * len, utab_rows() + (size_t)idx[first] * len, (size_t)run * len * sizeof(T), hipMemcpyDeviceToHost, stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(uf_stage.data() + first, uflag_rows() + idx[first], (size_t)run * sizeof(int), hipMemcpyDeviceToHost, stream);
+            });
+            const hipError_t es = hipStreamSynchronize(stream);
+            if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string("pddp_get_control_reference_problems: transfer failed: ") + hipGetErrorString(e != hipSuccess ? e : es));
+        }
+        for (int i = 0; i < count; i++) {
+            if (!uf_stage[i]) for (size_t e = 0; e < len; e++) U[(size_t)i * len + e] = T(0);      // no reference: what the control term subtracts, zero at every knot
+            if (has) has[i] = uf_stage[i] ? 1 : 0;
+        }
         return 0;
     }
     // ---- goal paths of the same plants (goal_path_table.hpp, k_goal_window in kernels.hpp): pddp_reserve_goal_path / pddp_set_goal_path_problems / ..._cursor_problems / pddp_get_...
@@ -1234,6 +1339,10 @@ struct Solver : SolverBase {
             if (int rc = in.reserve(in.d_dtab, (size_t)slot_chunk() * sizeof(T), "hipMalloc failed for the intake area's time steps")) return rc;
             in.b.dtab = in.dtab_rows();
         }
+        if (b.utab && !in.b.utab) {                                  // control references: the same, blocks and flags of the chunk's slots behind the intake's own zero row
+            if (int rc = in.reserve_ref_table(slot_chunk())) { in.d_utab.release(); in.d_uflag.release(); return rc; }      // (no half-made table stays behind, as in ensure_ref_table)
+            in.b.utab = in.utab_rows(); in.b.uflag = in.uflag_rows();
+        }
         if (!b.ABc) { in.b.ABc = nullptr; in.b.Hc = nullptr; }      // the handle left the compact layouts (ab_keep_reference_layout): so does its intake
         return ensure_slot_idx();
     }
@@ -1277,6 +1386,11 @@ struct Solver : SolverBase {
         }
         if (b.dtab) {                                                // ... and their time steps
             if (!slot_add(fetch, in.dtab_rows(), dtab_rows(), sizeof(T), sizeof(T), sizeof(T), kSlotCopy)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
+        }
+        if (b.utab) {                                                // ... and their control references: block and flag, next to the goal's
+            const size_t ub = ref_len() * sizeof(T);
+            if (!slot_add(fetch, in.utab_rows(), utab_rows(), ub, ub, ub, kSlotCopy) || !slot_add(fetch, in.uflag_rows(), uflag_rows(), sizeof(int), sizeof(int), sizeof(int), kSlotCopy))
+                return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
         }
         const size_t N = cfg.N;
         const int C = slot_chunk();
@@ -1339,8 +1453,11 @@ struct Solver : SolverBase {
         const Solver& in = *intake;
         const bool gt = b.gtab != nullptr;
         const bool st = b.dtab != nullptr;
-        const MpcSlotSide<T> is{b.cwt ? in.cwt_rows() : nullptr, in.d_xActual, in.d_goal_in, in.d_shift, gt ? in.gtab_rows() : nullptr, gt ? in.gflag_rows() : nullptr, st ? in.dtab_rows() : nullptr},
-                             hs{b.cwt ? cwt_rows() : nullptr, d_xActual, d_goal_in, d_shift, gt ? gtab_rows() : nullptr, gt ? gflag_rows() : nullptr, st ? dtab_rows() : nullptr};
+        const bool ut = b.utab != nullptr;
+        const MpcSlotSide<T> is{b.cwt ? in.cwt_rows() : nullptr, in.d_xActual, in.d_goal_in, in.d_shift, gt ? in.gtab_rows() : nullptr, gt ? in.gflag_rows() : nullptr, st ? in.dtab_rows() : nullptr,
+                                ut ? in.utab_rows() : nullptr, ut ? in.uflag_rows() : nullptr},
+                             hs{b.cwt ? cwt_rows() : nullptr, d_xActual, d_goal_in, d_shift, gt ? gtab_rows() : nullptr, gt ? gflag_rows() : nullptr, st ? dtab_rows() : nullptr,
+                                ut ? utab_rows() : nullptr, ut ? uflag_rows() : nullptr};
         return mpc_slot_tables<NX, NU, T>(in_t, out_t, in.b, in.mb, is, b, mb, hs, cfg.N, cfg.M, cfg.A, cfg.max_iter, cfg.ee_cost, table_record_len());
     }
     // pddp_mpc_slots_profile (measurement): HIP events around the in stage (movers + load kernel), the cycle and the out stage of every chunk

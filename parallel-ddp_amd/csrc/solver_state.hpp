@@ -76,7 +76,14 @@ struct Buffers {
     const T* gtab;       // [B][N][n] per-knot goal trajectories of the pendulum, cart-pole and quadrotor (plants.hpp GoalTab); null: every problem's goal is xGoal[b]
     const int* gflag;    // [B] with gtab: 1 = the problem's cost reads its rows of gtab, 0 = it reads xGoal[b]
     const T* dtab = nullptr;   // [B] per-problem time steps of the same plants (plants.hpp StepTab, problem_dt); null: every problem integrates with the kernel argument dt
+    const T* utab = nullptr;   // [B][N][m] control references of the same plants (plants.hpp RefTab), control_ref_pad<T>(m) zeros in front of row 0; null: every control term is taken on u itself
+    const int* uflag = nullptr;      // [B] with utab: 1 = the problem's control term reads u_k - utab[b][k], 0 = it reads the zero row in front of the table
 };
+
+// Buffers::utab: the zero row an unflagged problem reads sits in FRONT of the table, control_ref_pad<T>(m) elements -- whole 16-byte pieces, so that the rows behind it
+// keep the allocation's alignment (the quadrotor's float rows are read as one 16-byte load).  The allocation is pad + rows * N * m elements; utab points behind the pad.
+template <typename T>
+PDDP_HD constexpr int control_ref_pad(int nu) { return (int)(((size_t)nu * sizeof(T) + 15) / 16 * 16 / sizeof(T)); }
 
 // Rows of Buffers::cwt (plants.hpp cost_weights_at): 5 weights of the joint-space cost, 9 of the end-effector cost, in the argument order of pddp_set_cost / pddp_set_cost_ee.
 constexpr int kCostRecJoint = 5, kCostRecEe = 9;

@@ -410,6 +410,48 @@ class Solver:
         self.lib.pddp_clear_goal_trajectory_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._chk(self.lib.pddp_clear_goal_trajectory_problems(self.h, idx.size, _p(idx)))
 
+    # ---- control references (pendulum, cart-pole, quadrotor): the control term of a running knot on u_k - U[k]
+    def has_control_reference(self):
+        """True for the plants whose problems can carry a control reference (pendulum, cart-pole, quadrotor): set_control_reference_problems /
+        get_control_reference_problems / clear_control_reference_problems."""
+        return self.cfg.plant in (1, 2, 3)
+
+    def control_reference_size(self):
+        """pddp_control_reference_size: N * m numbers per problem, the references U[N][m] of the horizon's knots (row N - 1 is stored, never read); plants 1-3 only."""
+        self.lib.pddp_control_reference_size.argtypes = [C.c_void_p]
+        rc = self.lib.pddp_control_reference_size(self.h)
+        if rc <= 0:
+            self._chk(rc if rc else -1)
+        return rc
+
+    def set_control_reference_problems(self, idx, U):
+        """pddp_set_control_reference_problems: reference i of U (len(idx) x N x m numbers, any shape; converted to the handle's element type) for slot idx[i]: the
+        control term of its running knot k is taken on u_k - U[i][k].  In force for the following loads, solves and control cycles (follow it with load() or
+        load_problems(idx, ...)); the other slots keep theirs.  Control cycles do not shift the rows: write the new window before the cycle."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        U = self.arr(U).ravel()
+        if U.size != idx.size * self.control_reference_size():
+            raise PddpError(f"set_control_reference_problems: {idx.size} slots need {idx.size * self.control_reference_size()} numbers ({self.control_reference_size()} per reference), got {U.size}")
+        self.lib.pddp_set_control_reference_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_control_reference_problems(self.h, idx.size, _p(idx), _p(U)))
+
+    def get_control_reference_problems(self, idx):
+        """pddp_get_control_reference_problems: (U [len(idx)][N][m] in the handle's element type, has [len(idx)] int32).  has[i] = 1: slot idx[i] has a reference and
+        U[i] is its rows; 0: it has none and U[i] is zero."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        U = np.zeros((idx.size, self.cfg.N, self.m), self.dtype)
+        has = np.zeros(idx.size, np.int32)
+        self.control_reference_size()                     # (raises for plants 4 and 5 before the shapes above mean anything)
+        self.lib.pddp_get_control_reference_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_get_control_reference_problems(self.h, idx.size, _p(idx), _p(U), _p(has)))
+        return U, has
+
+    def clear_control_reference_problems(self, idx):
+        """pddp_clear_control_reference_problems: the named slots pay for u itself again, from the next load or solve on; a no-op on a handle that never had a table."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        self.lib.pddp_clear_control_reference_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(self.lib.pddp_clear_control_reference_problems(self.h, idx.size, _p(idx)))
+
     # ---- per-problem horizon times (pendulum, cart-pole, quadrotor)
     def set_horizon_time_problems(self, idx, times):
         """pddp_set_horizon_time_problems: times[i] seconds (len(idx) doubles) is the horizon time of slot idx[i]; its step is T(times[i] / (N - 1)), what a handle created
