@@ -109,6 +109,14 @@ template <> struct Mx<float> {
         asm volatile("ds_bpermute_b32 %0, %1, %2 offset:%3" : "=v"(r) : "v"(base_bytes), "v"(v), "n"(OFF));
         return r;
     }
+    // The same into a register the CALLER keeps live across the whole knot loop ("+v": the statement also reads it).  The compiler's hazard bookkeeping does not look
+    // into an asm: with a plain output it is free to hand the exchange a register that a matrix instruction issued just before still has to write (a dead element of its
+    // four-register result), and nothing then keeps the late matrix write from landing AFTER the lane has arrived -- the pivot row is gone, now and then.  Found in the
+    // listings of builds whose results varied from run to run on MI355X: an exchange zero wait states behind a v_mfma with its destination inside the v_mfma's; builds
+    // with at least one instruction between them reproduced.  A register that is live cannot be a matrix instruction's destination.
+    template <int OFF> static __device__ __forceinline__ void from_lane_into(float& r, float v, int base_bytes) {
+        asm volatile("ds_bpermute_b32 %0, %1, %2 offset:%3" : "+v"(r) : "v"(base_bytes), "v"(v), "n"(OFF));
+    }
     static __device__ __forceinline__ void lanes_arrived(float& a, float& b, float& c, float& before) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(before)); }
     static __device__ __forceinline__ void lane_arrived(float& a, float& before) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(before)); }
     template <int GO> static __device__ __forceinline__ float row_of_group(float v) { return __uint_as_float(mx_row_of_group<GO>(__float_as_uint(v))); }
@@ -145,6 +153,7 @@ template <> struct Mx<double> {
         asm volatile("ds_bpermute_b32 %0, %2, %3 offset:%5\n\tds_bpermute_b32 %1, %2, %4 offset:%5" : "=&v"(lo), "=&v"(hi) : "v"(base_bytes), "v"((unsigned)w), "v"((unsigned)(w >> 32)), "n"(OFF));
         return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
     }
+    template <int OFF> static __device__ __forceinline__ void from_lane_into(double& r, double v, int base_bytes) { r = from_lane_off<OFF>(v, base_bytes); }
     static __device__ __forceinline__ void lanes_arrived(double& a, double& b, double& c, double& before) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(before)); }
     static __device__ __forceinline__ void lane_arrived(double& a, double& before) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(before)); }
     template <int GO> static __device__ __forceinline__ double row_of_group(double v) {
@@ -267,8 +276,9 @@ __device__ __forceinline__ mx4t<T> mx_mfma2(const mx4t<T>& X, const mx4t<T>& Y, 
 template <typename T> __host__ __device__ constexpr int mx_pi(int b) { return Mx<T>::q_of(b >> 1, b & 1); }
 
 // One pivot of the distributed Gauss-Jordan inversion (arm_mx_bp_block): lane group g owns rows 2g, 2g + 1 (R0, R1) of [Huu | I].
+template <typename T> struct MxLanes { T prow, col0, col1; };              // where a pivot's three exchanged values arrive
 template <typename T, int PV>
-__device__ __forceinline__ void mx_gj_pivot(T& R0, T& R1, int g, int c4, int g64) {
+__device__ __forceinline__ void mx_gj_pivot(T& R0, T& R1, int g, int c4, int g64, MxLanes<T>& xl) {
     using X = Mx<T>;
     constexpr int go = PV >> 1;                                           // owner group of the pivot row; its register is PV & 1
     if (PDDP_MX_EXP == 1) return;
@@ -304,8 +314,9 @@ __device__ __forceinline__ void mx_gj_pivot(T& R0, T& R1, int g, int c4, int g64
         R1 = (g == go && (PV & 1)) ? q : n1;
         return;
     }
-    T prow = X::template from_lane_off<64 * go>(src, c4);
-    T col0 = X::template from_lane_off<4 * mx_pi<T>(PV)>(R0, g64), col1 = X::template from_lane_off<4 * mx_pi<T>(PV)>(R1, g64);
+    T &prow = xl.prow, &col0 = xl.col0, &col1 = xl.col1;                  // (registers that stay live over the loop: from_lane_into)
+    X::template from_lane_into<64 * go>(prow, src, c4);
+    X::template from_lane_into<4 * mx_pi<T>(PV)>(col0, R0, g64); X::template from_lane_into<4 * mx_pi<T>(PV)>(col1, R1, g64);
     T rp = X::recip(piv);                                                  // (issued before the wait: the reciprocal runs while the lanes travel)
     X::lanes_arrived(prow, col0, col1, rp);
     const T q = prow * rp;                                                // the scaled pivot row; row a loses (its pivot-column entry) x q
@@ -519,30 +530,66 @@ __device__ __forceinline__ void mx_dma_knot(const float* buf, mx_i4 dab, mx_i4 d
     if constexpr (HQQ)                                                // the knot's 49-float position block (b.Hc; 64 dwords: the over-read stays inside the array's slack)
         asm volatile("s_mov_b32 m0, %[l4]\n\ts_nop 0\n\tbuffer_load_dword %[v], %[dh], %[sh] offen lds" :: [l4] "s"(l0 + 16u * kMxDmaRegion), [v] "v"(lane4), [dh] "s"(dh), [sh] "s"(sh) : "memory", "m0");
 }
-// the knot's tile operands from its LDS copy (the selects of mx_load_knot_compact)
-// (aA .. aG: the lane's LDS BYTE addresses inside half 0 of the double buffer, kept opaque so that a knot pays one add per address; half: byte offset of the half)
+// Constant cells.  Which tile elements a lane must hold as zero depends on the lane alone, never on the knot, so such a lane does not read data and select it away on the
+// float32 lanes: its loop-invariant LDS address points at a cell that HOLDS zero (the LDS read path is not charged to those lanes).  The cells are dwords 32..63 of
+// region 3 in both halves of the double buffer -- the cost gradient's transfer runs on 32 lanes (mx_dma_knot), so no transfer ever writes them --, written once in front
+// of the knot loop: zero, but kMxCellQ1 / kMxCellQ2 = the position / velocity weight of the cost Hessian's diagonal (hq1, hq2: the same for every knot of a wave).
+// A lane's cost reads are base + {0, 1, 7, 8} (CXX[0..3]) and base + {14, 15} (CUX0, CUX1), base = mx_cost_base: the vector column's lanes read the knot's gradient, a
+// state column's lane whose register rd sits on the tile's diagonal reads the weight there and zeros around it, every other lane zeros -- the cost tile with ONE select
+// left (CUX1 of lane group 3, whose read lands behind the gradient's 21 floats; BT1 of lane group 3 likewise reads the over-read behind piece 2 and keeps its select).
+// The transfers themselves are the ones they were.
+constexpr int kMxGradFloats = 21, kMxGradLanes = 32;                   // the knot's cost gradient | dwords its transfer writes
+constexpr int kMxCellQ1 = 33, kMxCellQ2 = 55, kMxCellZ = 34;           // region 3: the two weights; the six reads from kMxCellZ find zeros (every lane that reads zeros only)
+__host__ __device__ constexpr int mx_cost_base(int g, int c) {
+    const int sc = mx_state<float>(c), rd = c - Mx<float>::q_of(g, 0);
+    if (sc == 14) return 2 * g;
+    if (sc < 14 && rd >= 0 && rd < 4) return rd < 2 ? kMxCellQ1 - rd : kMxCellQ2 - 7 - (rd & 1);   // (rd < 2: a position state, rd >= 2: a velocity state -- mx_state_gr)
+    return kMxCellZ;
+}
+constexpr bool mx_cost_cells_ok() {                                     // every read of every lane lands on the cell the tile wants there
+    constexpr int off[6] = {0, 1, 7, 8, 14, 15};
+    for (int lane = 0; lane < 64; lane++) {
+        const int g = lane >> 4, c = lane & 15, sc = mx_state<float>(c), base = mx_cost_base(g, c);
+        for (int i = 0; i < 6; i++) {
+            const int cell = base + off[i];
+            const bool zero_cell = cell >= kMxGradLanes && cell < kMxDmaRegion && cell != kMxCellQ1 && cell != kMxCellQ2;
+            if (cell < 0 || cell >= kMxDmaRegion) return false;
+            if (sc == 14) {                                            // g_x(state of register i) | g_u(2g), g_u(2g + 1)
+                const int want = i < 4 ? mx_state_gr(g, i) : 14 + 2 * g + (i - 4);
+                if (i < 4 && want >= 14) continue;                     // (padding / vector row of lane group 3: discarded by arm_mx_bp_block's select on the new cost-to-go's rows)
+                if (want >= kMxGradFloats) continue;                   // (CUX1 of lane group 3: mx_lds_knot's select)
+                if (cell != want) return false;
+            } else if (sc < 14 && i < 4 && Mx<float>::q_of(g, i) == c) {
+                if (cell != (sc < 7 ? kMxCellQ1 : kMxCellQ2)) return false;
+            } else if (!zero_cell) return false;
+        }
+    }
+    return true;
+}
+static_assert(mx_cost_cells_ok(), "constant cells of the matrix-core backward pass's operand buffer");
+// the knot's tile operands from its LDS copy (the operands of mx_load_knot_compact; what that one zeroes by selects is read as zero here)
+// (aA .. aG: the lane's LDS BYTE addresses inside half 0 of the double buffer -- its data, or constant cells -- kept opaque so that a knot pays one add per address;
+// half: byte offset of the half)
 template <bool FS>
-__device__ __forceinline__ void mx_lds_knot(MxKnotIn<float, FS, true>& k, unsigned half, unsigned aA, unsigned aB, unsigned aT, unsigned aG, int g, int c, int ub, float dt) {
-    constexpr int NX = 14, NU = 7;
+__device__ __forceinline__ void mx_lds_knot(MxKnotIn<float, FS, true>& k, unsigned half, unsigned aA, unsigned aB, unsigned aT, unsigned aG, int g, int c, float dt) {
+    constexpr int NX = 14;
     typedef const float __attribute__((address_space(3))) * lptr;
     const int u0 = 2 * g, sc = mx_state<float>(c);
-    const bool cx = sc < NX, cu = ub < NU, c14 = (sc == NX), g3 = g < 3;
+    const bool cx = sc < NX, g3 = g < 3;
     const lptr pA = (lptr)(size_t)(aA + half), pB = (lptr)(size_t)(aB + half), pT = (lptr)(size_t)(aT + half), pG = (lptr)(size_t)(aG + half);
     const float ta0 = pA[0], ta1 = pA[1], tb0 = pB[0], tb1 = pB[1];
     k.A0[0] = cx ? ((sc == u0) ? 1.f : ((sc == u0 + 7) ? dt : 0.f)) : 0.f;
     k.A0[1] = (cx && g3) ? ((sc == u0 + 1) ? 1.f : ((sc == u0 + 8) ? dt : 0.f)) : 0.f;
-    k.A0[2] = cx ? ta0 : 0.f; k.A0[3] = (cx && g3) ? ta1 : 0.f;
+    // lane group 3's second element is the first of the NEXT column (data, not a cell) and sits in the homogeneous row, which the products do sum over: that select stays
+    k.A0[2] = ta0; k.A0[3] = g3 ? ta1 : 0.f;
     k.B1[0] = 0.f; k.B1[1] = 0.f;
-    k.B1[2] = cu ? tb0 : 0.f; k.B1[3] = (cu && g3) ? tb1 : 0.f;
-    if (FS) {
-        const float t0 = pT[0], t1 = pT[7];
-        k.BT0 = (cx && sc >= 7) ? t0 : 0.f; k.BT1 = (cx && sc >= 7 && u0 + 1 < NU) ? t1 : 0.f;
-    }
-    const float gx[4] = {pG[0], pG[1], pG[7], pG[8]};
-    const float gu0 = pG[NX], gu1 = pG[NX + 1];
-#pragma unroll
-    for (int r = 0; r < 4; r++) k.CXX[r] = (c14 && (g3 || !(r & 1))) ? gx[r] : 0.f;
-    k.CUX0 = c14 ? gu0 : 0.f; k.CUX1 = (c14 && u0 + 1 < NU) ? gu1 : 0.f;
+    k.B1[2] = tb0; k.B1[3] = g3 ? tb1 : 0.f;
+    if (FS) { k.BT0 = pT[0]; k.BT1 = g3 ? pT[7] : 0.f; }               // (lane group 3: "control 7" is the transfer's over-read behind piece 2)
+    // (lane 63 -- vector column, lane group 3 -- reads g_x(7) and g_u(0) into its padding and vector rows.  They are ADDED into elements 1, 3 of Hxx of that lane and of
+    // no other, Hxx feeds nothing but Pn = Hxx + val, and Pn[1], Pn[3] of lane group 3 are replaced by a SELECT of zero, not multiplied by one: whatever they hold,
+    // infinities and NaNs included, ends there)
+    k.CXX[0] = pG[0]; k.CXX[1] = pG[1]; k.CXX[2] = pG[7]; k.CXX[3] = pG[8];
+    k.CUX0 = pG[NX]; k.CUX1 = g3 ? pG[NX + 1] : 0.f;
     k.hx = 0.f; k.hu = 0.f;
 }
 
@@ -652,6 +699,7 @@ __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int
         for (int r = 0; r < 4; r++) PsiT[r] = (diag[r] && sc <= NX) ? T(1) : T(0);
     }
     MxKnotIn<T, FS, DIAGH> in;
+    MxLanes<T> xl = {T(0), T(0), T(0)};                               // (live from here to the end of the loop: mx_gj_pivot's exchanges arrive in them)
     T hq0 = T(0), hq1v = T(0);                                        // HQQ: this lane's two entries of the knot's position block
     const T* ABk = AB + (size_t)ks * SZAB; const T* Hk = H + (size_t)ks * SZH; const T* gk = gg + (size_t)ks * NM;   // running block pointers (wave-uniform)
     T* KTk = KT + (size_t)ks * (NX * NU); T* duk = du + (size_t)ks * NU; T* Fk = ApBK + (size_t)ks * SZP; T* Bduk = Bdu + (size_t)ks * NX;
@@ -679,11 +727,21 @@ __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int
     if constexpr (DMA) {
         const int cc = cx ? sc : NX - 1, uc = cu ? ub : NU - 1;
         const unsigned l0 = (unsigned)(size_t)(__attribute__((address_space(3))) const float*)dmaLds;
-        aA = l0 + 4u * (unsigned)(abc_piece(cc) * kMxDmaRegion + abc_col_in_piece(cc) * 7 + 2 * g);
-        aB = l0 + 4u * (unsigned)(2 * kMxDmaRegion + uc * 7 + 2 * g);
-        aT = l0 + 4u * (unsigned)(2 * kMxDmaRegion + u0 * 7 + (cx && sc >= 7 ? sc - 7 : 0));
-        aG = l0 + 4u * (unsigned)(3 * kMxDmaRegion + 2 * g);
+        // the lane's operand addresses, decided once: its data where the tile has data, constant cells where it has zeros or the cost weights (mx_lds_knot)
+        const unsigned lz = l0 + 4u * (unsigned)(3 * kMxDmaRegion + kMxCellZ);
+        aA = cx ? l0 + 4u * (unsigned)(abc_piece(cc) * kMxDmaRegion + abc_col_in_piece(cc) * 7 + 2 * g) : lz;
+        aB = cu ? l0 + 4u * (unsigned)(2 * kMxDmaRegion + uc * 7 + 2 * g) : lz;
+        aT = (cx && sc >= 7) ? l0 + 4u * (unsigned)(2 * kMxDmaRegion + u0 * 7 + (sc - 7)) : lz;
+        aG = l0 + 4u * (unsigned)(3 * kMxDmaRegion + mx_cost_base(g, c));
         asm volatile("" : "+v"(aA), "+v"(aB), "+v"(aT), "+v"(aG));
+        {
+            float* cw = const_cast<float*>(dmaLds);                   // lanes 0..31: the cells of half 0, lanes 32..63: of half 1; then the two weights
+            static_assert(kMxDmaRegion - kMxGradLanes == 32, "one lane per cell and half");
+            cw[(lane >> 5) * kMxDmaBuf + 3 * kMxDmaRegion + kMxGradLanes + (lane & 31)] = 0.f;
+            wsync();
+            if (lane < 2) { cw[lane * kMxDmaBuf + 3 * kMxDmaRegion + kMxCellQ1] = hq1; cw[lane * kMxDmaBuf + 3 * kMxDmaRegion + kMxCellQ2] = hq2; }
+            wsync();
+        }
         dab = mx_desc(b.ABc + (knot0 >> 6) * kAbcChunk); dgg = mx_desc(gg);
         if constexpr (HQQ) {
             aH = l0 + 4u * (unsigned)(4 * kMxDmaRegion + (sc < 7 ? sc : 6) * 7 + (g < 3 ? 2 * g : 5));
@@ -716,7 +774,7 @@ __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int
                 else if (keepP) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kMxGainStores + kMxCtgStores) : "memory");
 #endif
                 else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kMxGainStores) : "memory");
-                mx_lds_knot<FS>(in, (unsigned)par * (unsigned)(4 * kMxDmaBuf), aA, aB, aT, aG, g, c, ub, dt);
+                mx_lds_knot<FS>(in, (unsigned)par * (unsigned)(4 * kMxDmaBuf), aA, aB, aT, aG, g, c, dt);
                 if constexpr (HQQ) {
                     typedef const float __attribute__((address_space(3))) * lptr;
                     const lptr pH = (lptr)(size_t)(aH + (unsigned)par * (unsigned)(4 * kMxDmaBuf));
@@ -743,8 +801,10 @@ __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int
         // ---- cost blocks in tile form
         mx4 CXX = k.CXX, CUX = {k.CUX0, k.CUX1, T(0), T(0)}, CXU = zero, CUU = zero;
         if (DIAGH) {
+            if constexpr (!DMA) {                                     // (the prefetching variants read the diagonal with the gradient: constant cells, mx_lds_knot)
 #pragma unroll
-            for (int r = 0; r < 4; r++) if (cx) CXX[r] = diag[r] ? (sc < 7 ? hq1 : hq2) : T(0);
+                for (int r = 0; r < 4; r++) if (cx) CXX[r] = diag[r] ? (sc < 7 ? hq1 : hq2) : T(0);
+            }
             CUU[0] = (cu && u0 == ub) ? hr : T(0); CUU[1] = (cu && u0 + 1 == ub) ? hr : T(0);
             if (HQQ) {                                                // rows 2g, 2g + 1 of column sc of the position block (symmetric: read as column sc, rows 2g..)
                 typename X::v2u hv;
@@ -802,7 +862,7 @@ __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int
             HxuT = mx_mfma_hi<T>(W1, k.A0, lowW) + CXU;
             __builtin_amdgcn_sched_barrier(0);
             mx_gj_finish<T, 3>(fl, R0, R1, g);
-            mx_gj_pivot<T, 4>(R0, R1, g, c4, g64); mx_gj_pivot<T, 5>(R0, R1, g, c4, g64); mx_gj_pivot<T, 6>(R0, R1, g, c4, g64);
+            mx_gj_pivot<T, 4>(R0, R1, g, c4, g64, xl); mx_gj_pivot<T, 5>(R0, R1, g, c4, g64, xl); mx_gj_pivot<T, 6>(R0, R1, g, c4, g64, xl);
             if (cr >= 2 && e < NU) { ldsI[wa - X::q_of(0, 2)] = R0; ldsI[wa + 16 - X::q_of(0, 2)] = R1; }
             wsync();
         } else {
@@ -864,8 +924,8 @@ __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int
             }
             wsync();
         } else {
-        mx_gj_pivot<T, 0>(R0, R1, g, c4, g64); mx_gj_pivot<T, 1>(R0, R1, g, c4, g64); mx_gj_pivot<T, 2>(R0, R1, g, c4, g64); mx_gj_pivot<T, 3>(R0, R1, g, c4, g64);
-        mx_gj_pivot<T, 4>(R0, R1, g, c4, g64); mx_gj_pivot<T, 5>(R0, R1, g, c4, g64); mx_gj_pivot<T, 6>(R0, R1, g, c4, g64);
+        mx_gj_pivot<T, 0>(R0, R1, g, c4, g64, xl); mx_gj_pivot<T, 1>(R0, R1, g, c4, g64, xl); mx_gj_pivot<T, 2>(R0, R1, g, c4, g64, xl); mx_gj_pivot<T, 3>(R0, R1, g, c4, g64, xl);
+        mx_gj_pivot<T, 4>(R0, R1, g, c4, g64, xl); mx_gj_pivot<T, 5>(R0, R1, g, c4, g64, xl); mx_gj_pivot<T, 6>(R0, R1, g, c4, g64, xl);
         if (cr >= 2 && e < NU) { ldsI[wa - X::q_of(0, 2)] = R0; ldsI[wa + 16 - X::q_of(0, 2)] = R1; }   // identity column e sits two registers along: tile column mx_pi(e)
         wsync();
         }
@@ -931,10 +991,12 @@ __device__ void arm_mx_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, int
         if (FS) {                                                     // A - B K | B du  (computeFSVars :281-312)
             const mx4 BT = {k.BT0, k.BT1, T(0), T(0)};                                            // [b][kx = c] = B(kx, b)
             const mx4 BK = mx_mfma2<T>(BT, Kp, zero);
-            mx4 Gt = c14 ? BK : k.A0 - BK;                                                        // [A - B K | B du]; the padding / vector rows are zero
+            mx4 Gt;                                                                               // [A - B K | B du]; the padding / vector rows are zero
+#pragma unroll
+            for (int r = 0; r < 4; r++) Gt[r] = c14 ? BK[r] : k.A0[r] - BK[r];                    // (element by element: one select each; as a whole-tile select the compiler spends three)
             if (!FUSE) mx_store_col<T>(cx ? Fk + sc * NX : Bduk, g, cx || c14, Gt);
             if (FUSE && fuse) {
-                if (c14 && g == 3) Gt[3] = T(1);                                                  // G(14, 14) = 1: the homogeneous coordinate (lane group 3, register 3)
+                Gt[3] = (c14 && g == 3) ? T(1) : Gt[3];                                           // G(14, 14) = 1: the homogeneous coordinate (lane group 3, register 3)
                 if (CAB) {                                                                        // position rows of G are [I  dt I | 0] (B is zero there): as for Hxx
                     const mx4 low = {PsiT[0], PsiT[1], dt * PsiT[0], dt * PsiT[1]};
                     PsiT = mx_mfma_hi<T>(Gt, PsiT, low);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """ISA of the matrix-core translation unit (csrc/pddp_mx.hip) for gfx950: per-kernel resources, and the body of one kernel to a file.
-usage: tools/mx_isa.py [-D...] [--dump <regex on the mangled name> <file>]      (cross-compiles: no GPU needed)"""
+usage: tools/mx_isa.py [-D...] [--mix <regex on the mangled name>] [--dump <regex on the mangled name> <file>]      (cross-compiles: no GPU needed)"""
 import os, re, subprocess, sys
 pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "parallel-ddp_amd")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-Wno-unused-result", "-Wno-unused-value", "-fno-slp-vectorize"]
@@ -42,11 +42,64 @@ def resources(remarks):
     return out
 
 
+def knot_loop_range(body):
+    """(first, last) line index of the knot loop of one kernel body, or None.  The loop's blocks carry the header's name in their comments; the cycle may enter through a
+    block the compiler placed in front of the header (inside the loop, or right in front of it: the hoisted all-slots wait) -- a block that back edges target belongs to it."""
+    hdr = next((i for i, l in enumerate(body) if "Inner Loop Header" in l), None)
+    if hdr is None:
+        return None
+    name = re.match(r"^\.L(BB\d+_\d+):", body[hdr]).group(1)
+    blocks = [i for i, l in enumerate(body) if re.match(r"^\.LBB\d+_\d+:", l) and ("Inner Loop Header" in l or "in Loop: Header=" + name + " " in l)]
+    labels = [body[i].split(":")[0].strip() for i in blocks]
+    first = min(blocks)
+    def targets(l, lab):
+        return re.search(r"s_c?branch\S*\s+" + re.escape(lab) + r"\b", l)
+    pre = next((i for i in range(first - 1, max(first - 12, 0), -1) if re.match(r"^\.LBB\d+_\d+:", body[i])), None)
+    if pre is not None:
+        pre_label = body[pre].split(":")[0].strip()
+        if any(targets(body[i], pre_label) for i in range(first, len(body))):
+            labels.append(pre_label); first = pre
+    back = [i for i in range(first, len(body)) if any(targets(body[i], lab) for lab in labels)]
+    return (first, back[-1]) if back else None
+
+
+def knot_loop_mix(body):
+    """Static instruction mix of one pass of the knot loop, by kind; None without a loop.
+    Vector instructions by opcode (matrix instructions as "mfma"), everything else by class."""
+    import collections
+    rng = knot_loop_range(body)
+    if rng is None:
+        return None
+    start, back = rng[0], [rng[1]]
+    mix = collections.Counter()
+    for l in body[start:back[-1] + 1]:
+        t = l.strip()
+        if not l.startswith("\t") or not t or t[0] in ".;":
+            continue
+        op = t.split()[0]
+        if op.startswith("v_mfma"): mix["mfma"] += 1
+        elif op.startswith("v_readlane") or op.startswith("v_readfirstlane"): mix["v_readlane"] += 1
+        elif op.startswith("v_"): mix[re.sub(r"_(e32|e64|dpp|sdwa)$", "", op)] += 1; mix["valu (no mfma, no readlane)"] += 1
+        elif op == "ds_bpermute_b32": mix["ds_bpermute"] += 1
+        elif op.startswith("ds_"): mix["ds other"] += 1
+        elif op.startswith("buffer_"): mix["buffer"] += 1
+        elif op == "s_nop": mix["s_nop"] += 1
+        elif op.startswith("s_"): mix["salu"] += 1
+        else: mix[op] += 1
+    return mix
+
+
 if __name__ == "__main__":
     defs = [a for a in sys.argv[1:] if a.startswith("-D")]
     asm, rem = compile_asm(defs=defs)
     for nm, d in resources(rem).items():
         print(f"{nm[:72]:72s} {d}")
+    if "--mix" in sys.argv:                                               # --mix <regex on the mangled name>: the knot loop's instruction mix of every kernel that matches
+        pat = re.compile(sys.argv[sys.argv.index("--mix") + 1])
+        for nm, body in kernel_bodies(asm).items():
+            mix = knot_loop_mix(body) if pat.search(nm) else None
+            if mix:
+                print(nm[:72], "knot loop:", ", ".join(f"{k} {v}" for k, v in sorted(mix.items(), key=lambda kv: -kv[1])))
     if "--dump" in sys.argv:
         i = sys.argv.index("--dump")
         pat = re.compile(sys.argv[i + 1])
@@ -64,20 +117,11 @@ K_GAIN, K_CTG = 4, 3
 def prefetch_loop_ops(body):
     """The memory-side instruction sequence of the knot loop of one k_bp_mfma instantiation, in program order:
     ("dma" | "load" | "gain" | "store" | "wait:<n>" | "cwait:<n>", text).  dma = buffer_load ... lds; gain = a buffer store of any width; store = any other store;
-    wait = an s_waitcnt vmcnt(n) of the source's inline assembly, cwait = one the compiler placed; the loop = the cycle around the "Inner Loop Header" label."""
-    hdr = next((i for i, l in enumerate(body) if "Inner Loop Header" in l), None)
-    if hdr is None:
+    wait = an s_waitcnt vmcnt(n) of the source's inline assembly, cwait = one the compiler placed; the loop = knot_loop_range."""
+    rng = knot_loop_range(body)
+    if rng is None:
         return None
-    label = body[hdr].split(":")[0].strip()
-    # a block right in front of the header that every back edge may also target (the compiler hoists the all-slots wait there)
-    pre = next((i for i in range(hdr - 1, max(hdr - 12, 0), -1) if re.match(r"^\.LBB\d+_\d+:", body[i])), None)
-    pre_label = body[pre].split(":")[0].strip() if pre is not None else None
-    def targets(l, lab):
-        return lab is not None and re.search(r"s_c?branch\S*\s+" + re.escape(lab) + r"\b", l)
-    back = [i for i in range(hdr, len(body)) if targets(body[i], label) or targets(body[i], pre_label)]
-    if not back:
-        return None
-    start = pre if (pre_label and any(targets(body[i], pre_label) for i in back)) else hdr
+    start, back = rng[0], [rng[1]]
     ops, in_asm = [], False
     for l in body[start:back[-1] + 1]:
         t = l.strip()
