@@ -92,6 +92,20 @@ inline FpPath select_fp_path(const char* name, bool is_float, bool /*ee_cost*/, 
     return select_fp_path(sel, is_float, tl_model_ok, batch);
 }
 
+// How k_fp_lg (kernels.hpp) divides a problem's candidates over workgroups: grid (batch, chunks), A / chunks candidates per workgroup, one 8-lane group per (candidate,
+// segment), eight groups per wave.  One workgroup per 8 candidates when A is a multiple of 8 above 8, all of them in one workgroup otherwise -- unless that workgroup
+// would need more than 128 groups (1024 threads, the largest k_fp_lg instantiation and the device's limit): then the largest divisor of A that fits.  One candidate per
+// workgroup always fits (M <= 16), so every accepted (M, A) has a launch.  A candidate's rollouts and its cost reduction never look at another candidate's (fp_reduce:
+// one wave per candidate over that candidate's own row of per-knot costs), so the division changes no bit.  `create` sizes the dynamic LDS by the same per_wg.
+constexpr int kFpLgMaxGroups = 128;
+struct FpLgChunks { int chunks, per_wg, waves, size; };      // size: the instantiation, 0 up to 256 threads, 1 512, 2 1024
+inline FpLgChunks fp_lg_chunks(int A, int M) {
+    int per_wg = (A > 8 && A % 8 == 0) ? 8 : A;
+    if (per_wg * M > kFpLgMaxGroups) { per_wg = kFpLgMaxGroups / M; while (A % per_wg) per_wg--; }
+    const int waves = (per_wg * M + 7) / 8;
+    return {A / per_wg, per_wg, waves, waves <= 4 ? 0 : waves <= 8 ? 1 : 2};
+}
+
 struct PlantTraits { int plant, NX, NU; bool scalar_plugin, plugin_cost; };      // P::PLANT, P::NX, P::NU, P::kScalarPlugin, P::kPluginCost
 
 struct KernelPlan {

@@ -97,9 +97,11 @@ __global__ __launch_bounds__(64) void k_sweep_lg(Buffers<T> b, Dims dm, T dt) {
     arm_lg_forward_sweep<LgDevice<T>, T>(dm, a);
 }
 // k_fp_lg: grid (B, C), block 64 * ceil(Ac*M/8) with Ac = A / C candidates per workgroup: group i of the block rolls out segment i / Ac of candidate
-// a0 + i % Ac (the 8 groups of a wave are 8 candidates of one segment: they read the same gains, which the memory pipeline coalesces); per-knot
-// costs meet in LDS and are tree-summed per candidate in the reference's pairing.  Dynamic LDS: Ac*(N+M) elements.  C > 1 (A a multiple of 8 above 8:
-// one workgroup per 8 candidates) spreads one problem over C compute units -- the same waves in total, half the latency per sweep for A = 16.
+// a0 + i % Ac (with Ac = 8 the 8 groups of a wave are 8 candidates of one segment: they read the same gains, which the memory pipeline coalesces; with
+// another Ac a wave runs on into the next segment, which changes no result); per-knot costs meet in LDS and are tree-summed per candidate in the
+// reference's pairing, one candidate's row at a time.  Dynamic LDS: Ac*(N+M) elements.  C and Ac come from fp_lg_chunks (kernel_plan.hpp): C > 1 for
+// A a multiple of 8 above 8 (one workgroup per 8 candidates: one problem over C compute units -- the same waves in total, half the latency per sweep
+// for A = 16), and wherever A * M > 128 lane groups (the largest divisor of A that fits: Ac = 6 for M = 16, A = 12, Ac = 1 for a prime A).
 template <typename T, int MAXT, bool EE = false>
 __global__ __launch_bounds__(MAXT, 1) void k_fp_lg(Buffers<T> b, Dims dm, CostWeights<T> cw, T dt, int init_rollout) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];

@@ -48,9 +48,7 @@ extern "C" int pddp_create(const pddp_config* cfg, pddp_handle* out) {
     if (!cfg || !out) return fail(PDDP_EINVAL, "null argument");
     const pddp_config& c = *cfg;
     if (const char* complaint = pddp::config_complaint(c, kMaxPlant); complaint[0]) return fail(PDDP_EINVAL, complaint);
-    // the arm's lane-group kernels: 128 rollouts per workgroup, 32-bit element offsets
-    if (c.plant == 4 && ((c.A > 8 && c.A % 8 == 0) ? 8 : c.A) * c.M > 128)
-        return fail(PDDP_EINVAL, "KUKA arm: (candidates per workgroup) * M must not exceed 128 -- a workgroup rolls out 8 candidates when A is a multiple of 8, otherwise all A");
+    // the arm's lane-group kernels: 32-bit element offsets (their 128 rollouts per workgroup are no limit on A: kernel_plan.hpp fp_lg_chunks divides the candidates)
     if (c.plant == 4 && (double)c.batch * c.N * (c.A * 14 > 441 ? c.A * 14 : 441) >= 4294967296.0)
         return fail(PDDP_EINVAL, "KUKA arm: batch * N too large for the 32-bit element offsets of the lane-group kernels (split the batch over several handles)");
     SolverBase* s = make_solver(c);

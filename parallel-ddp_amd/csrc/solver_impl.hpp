@@ -204,8 +204,7 @@ struct Solver : SolverBase {
         }
         fp_lds = FpLds<P, T>::bytes(c.M, c.N);
         if constexpr (P::PLANT == 4) {                                 // lane-group forward pass: A * (N + M) elements of dynamic LDS per workgroup
-            const size_t a_wg = (c.A > 8 && c.A % 8 == 0) ? 8 : c.A;       // candidates per workgroup (launch_fp_rollouts)
-            const size_t lds = a_wg * (c.N + c.M) * sizeof(T);
+            const size_t lds = (size_t)fp_lg_chunks(c.A, c.M).per_wg * (c.N + c.M) * sizeof(T);      // candidates per workgroup: the rule launch_fp_rollouts follows
             if (lds > 160 * 1024) return fail(PDDP_EINVAL, "forward-pass LDS footprint (candidates per workgroup * (N + M) elements) exceeds 160 KiB: reduce A or N");
             if (lds > 48 * 1024) {
                 for (int k = 0; k < 6; k++) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fp_lg_kernel(k % 3, k >= 3)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -324,10 +323,8 @@ struct Solver : SolverBase {
             break;
         case kFpKernLg:
             if constexpr (P::PLANT == 4) {
-                const unsigned chunks = (A_all > 8 && A_all % 8 == 0) ? A_all / 8 : 1;      // one workgroup per 8 candidates when they tile exactly (see k_fp_lg)
-                const int A_eff = A_all / chunks;
-                const unsigned waves = (A_eff * cfg.M + kLgPerWave - 1) / kLgPerWave;
-                hipLaunchKernelGGL(fp_lg_kernel(waves <= 4 ? 0 : waves <= 8 ? 1 : 2, cfg.ee_cost != 0), dim3(B, chunks), dim3(64 * waves), (size_t)A_eff * (cfg.N + cfg.M) * sizeof(T), s,
+                const FpLgChunks c = fp_lg_chunks(A_all, cfg.M);            // (kernel_plan.hpp: never more than 1024 threads)
+                hipLaunchKernelGGL(fp_lg_kernel(c.size, cfg.ee_cost != 0), dim3(B, c.chunks), dim3(64 * c.waves), (size_t)c.per_wg * (cfg.N + cfg.M) * sizeof(T), s,
                                    b, dm, cw, dt, L.seed == 1 ? 1 : 0);
             }
             break;
