@@ -420,6 +420,40 @@ int pddp_control_reference_size(pddp_handle h);                                 
 int pddp_set_control_reference_problems(pddp_handle h, int count, const int* idx, const void* U /* [count][N][m], handle dtype */);
 int pddp_get_control_reference_problems(pddp_handle h, int count, const int* idx, void* U /* [count][N][m] */, int* has /* [count], may be NULL */);
 int pddp_clear_control_reference_problems(pddp_handle h, int count, const int* idx);
+/* Control limits of the same plants (pendulum, cart-pole, quadrotor): hard bounds lo <= u_k <= hi on every running knot's control -- actuators
+ * that saturate -- by control-limited DDP (Tassa, Mansard and Todorov, ICRA 2014).  A problem of such a handle either has a limit row
+ * lo_0..lo_{m-1} | hi_0..hi_{m-1} (doubles, rounded to the handle's element type), or it has none.  -inf and +inf are legal entries: no bound on that side.
+ *   with a row: (1) the backward pass forms Qx, Qu, Qxx, Qux, Quu of every running knot as always (the regularisation by rho and the test on the full Quu that drives
+ *     the rho retry included); du is then the minimiser of 1/2 du' Quu du - Qu' du over  ucur_k - hi <= du <= ucur_k - lo, so that ucur_k - du lies inside the limits
+ *     at alpha = 1 (the box is never empty, even where ucur_k is outside).  Controls whose component of du sits on a bound with the multiplier pointing outward are
+ *     CLAMPED: their rows of K are zero, the free rows are Quu_ff^-1 Qux_f, and the cost-to-go takes the form that holds for any K, du:
+ *     P = Qxx + K' Quu K - K' Qux - Qux' K,  p = Qx + K' Quu du - K' Qu - Qux' du.  dJexp keeps its expressions in du, Qu, Quu.  A knot with no clamped control
+ *     computes what the cooperative backward pass computes, bit for bit.  A knot whose box step (an active-set walk over the clamped set) does not settle within a fixed number of faces fails
+ *     the backward pass of its problem like a failed Quu test: rho is raised and bp_retries counts it.
+ *     (2) every place that applies the control law clamps the result: u = min(max(ucur - alpha du - K dx, lo), hi) -- the rollouts of every family, the load's initial
+ *     rollout, the feedback part of the warm start of a control cycle.  A load does NOT clamp the caller's u0, a control cycle does not clamp the shifted previous
+ *     controls.  The linear sweeps, the line search, setup, cost and THE SIMULATORS are unchanged: the simulated robot (pddp_simulate*) applies the plan's law
+ *     u + K (x_plan - x) unclamped, as the reference's getHardwareControls does -- a caller who wants a saturating robot clips there.
+ *   without one: the problem behaves as it always did (it reads the row -inf.. | +inf.., and min(max(u, -inf), +inf) is u bit for bit).
+ * Timing, first call, refusals and named slots are those of pddp_set_control_reference_problems: limits are in force for the following loads, solves and control cycles;
+ * problems that are not named keep theirs; the first setter call gives the handle a device table [batch][2 m] in its element type -- and, where it has none, the
+ * reference, step, goal and cost tables the way the first pddp_set_control_reference_problems call creates them -- and drops the captured sweep graph once; later
+ * calls only write rows (on the solver's stream, one synchronisation before the call returns).  A handle that never calls the setter launches exactly the kernels and
+ * arguments it launches without these entry points.  A handle WITH a table launches k_bp_box (csrc/bp_box.hpp) for its backward pass whatever its kernel selection
+ * says -- a full-device quadrotor handle gives up the matrix-core backward pass and the fused sweep maps --, and pddp_time_kernels keeps reporting the SELECTION's
+ * name in slot 0 for it, and where the selection's sweep applies composed maps (k_sweep_maps_cf) it keeps that name in slot 1 while k_sweep_cf runs.
+ * pddp_run_phase(PDDP_PHASE_BP) launches k_bp_box on such a handle, PDDP_PHASE_BP_COOP the cooperative kernel without limits; PDDP_PHASE_BP_FUSED and
+ * PDDP_PHASE_SWEEP_FUSED are refused with PDDP_EINVAL (there are no maps).
+ * pddp_load_problems, pddp_mpc_solve_problems and pddp_mpc_load_problems run the named slots with their own rows; nothing is written back.
+ * pddp_get_control_limits_problems returns the stored rows (as rounded) and has[i] = 1 for a problem with limits; for a problem without (and for every problem before
+ * the first setter call) -inf.. | +inf.. and has[i] = 0.  has may be NULL.  pddp_clear_control_limits_problems: the named problems are unlimited again; on a handle that
+ * never had a table a successful no-op.
+ * PDDP_EINVAL, with the handle unchanged: plants 4 and 5 (the arm keeps its soft use_limits penalty); count < 1; a NULL idx or lim; an index
+ * outside [0, batch); an index named twice; (setter) a NaN, or lo_j >= hi_j after rounding to the element type.  The handle need not be loaded yet. */
+int pddp_control_limits_size(pddp_handle h);                                    /* 2 * m */
+int pddp_set_control_limits_problems(pddp_handle h, int count, const int* idx, const double* lim /* [count][2*m]: lo_0..lo_{m-1} | hi_0..hi_{m-1} */);
+int pddp_get_control_limits_problems(pddp_handle h, int count, const int* idx, double* lim /* [count][2*m] */, int* has /* [count], may be NULL */);
+int pddp_clear_control_limits_problems(pddp_handle h, int count, const int* idx);
 /* ---- the lock-step experiment around the solver ------------------------- */
 /* simulateForward<T, SUBSTEPS> (examples/WAFR_MPC_examples.cu:111-139): the simulated robot of the lock-step MPC experiment.  Starting
  * from xActual at plant time t0_us (the plan's t0), integrates the plant IN DOUBLE for elapsed_us in `substeps` steps under the trajectory

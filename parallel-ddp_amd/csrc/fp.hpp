@@ -111,6 +111,7 @@ PDDP_HD void forward_sim_segment(const Wave& w, SimScratch<P, T>& s, const Dims&
             for (int c = 0; c < NX; c++) Kdx += KTk[c + r * NX] * s.dx[c];
             T uv = a.ucur[NU * kn + r];
             uv -= a.alpha * a.du[NU * kn + r] + Kdx;
+            if constexpr (IsLimTab<P>::value) uv = control_clamp(uv, xg.lim, r, NU);      // (control limits: the problem's row travels with its goal, plants.hpp)
             s.u[r] = uv; a.u[NU * kn + r] = uv;
         }
         wsync();

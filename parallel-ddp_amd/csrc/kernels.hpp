@@ -10,6 +10,7 @@
 #include "nis_lg.hpp"
 #include "bp_lg.hpp"
 #include "bp_cl.hpp"
+#include "bp_box.hpp"
 #include "bp_mq.hpp"
 #include "kernel_plan.hpp"
 #include "goal_path_table.hpp"
@@ -448,6 +449,15 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
         ut_on = lane < PW * NU && b.uflag[q] != 0;
         if (lane < PW * NU) { (&stage[0].ro.ug[0][0])[lane] = T(0); (&stage[1].ro.ug[0][0])[lane] = T(0); }
     }
+    // control limits (LimTab, plants.hpp): the rows of the wavefront's problems, constant over the knots, staged in LDS once; the control law reads its problem's copy
+    [[maybe_unused]] const T* lim = nullptr;
+    if constexpr (IsLimTab<P>::value && PART == 1) {
+        __shared__ T lim_s[PW][2 * NU];
+        static_assert(PW * 2 * NU <= 64, "one element of the limit rows per lane");
+        const int p = lane / (2 * NU), q = (pb0 + p < batch) ? pb0 + p : batch - 1;
+        if (lane < PW * 2 * NU) (&lim_s[0][0])[lane] = b.ltab[(size_t)q * 2 * NU + (lane - p * 2 * NU)];
+        lim = lim_s[grp];
+    }
     const T alpha = b.alpha[a_idx];
     // the current trajectory sits in one half of xb per PROBLEM (state.cur): this lane's share of the state fetch is entry e of problem p
     const __amdgpu_buffer_rsrc_t r_xcur = mx_rsrc(b.xb + (size_t)pb0 * 2 * N * NX);
@@ -552,6 +562,7 @@ __device__ __forceinline__ void fp_cf_body(FpCfStage<P, T, A>* stage, T (*goal_s
             PDDP_UNROLL for (int c = 0; c < NX; c++) Kdx += sc.ro.K[grp][c + r * NX] * dx[c];
             T uv = sc.ro.up[grp][r];
             uv -= alpha * sc.ro.du[grp][r] + Kdx;
+            if constexpr (IsLimTab<P>::value) uv = control_clamp(uv, lim, r, NU);
             u[r] = uv;
         }
         if constexpr (IsRefTab<P>::value) cost_k[k] = P::cost(cw, x, u, KnotRef<T>{sc.ro.xg[grp], sc.ro.ug[grp]}, k, N);      // knot k's goal and control reference, from the stage
@@ -914,6 +925,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) ==
     a.err = b.err + (size_t)pb * dm.M;
     a.rho = st.rho;
     if (bp_cl_block<P, T>(s[grp], c, dm, blk, a, diag_h != 0, knot_weight<P, T>(b, cw, pb, c, 0, N))) { if (c == 0) a.err[blk] = 1; }
+}
+
+// k_bp_box: the backward pass of a handle with control limits (bp_box.hpp): 16 lanes = (problem, block of knots), lane = column of [A B] / H, the box step of every knot
+// solved redundantly in the unit's registers; grid ceil(B M / 4), block 64.  Not a plan choice: launch_bp launches it wherever Buffers::ltab exists.
+template <typename P, typename T>
+__global__ __launch_bounds__(64) void k_bp_box(Buffers<T> b, Dims dm, int batch) {
+    __shared__ BpBoxLds<P, T> s[4];
+    const int grp = threadIdx.x >> 4, c = threadIdx.x & 15, inst = blockIdx.x * 4 + grp;
+    if (inst >= batch * dm.M) return;
+    constexpr int NX = P::NX, NU = P::NU, NM = NX + NU;
+    const int blk = inst % dm.M, pb = inst / dm.M, N = dm.N;
+    const SolverState<T>& st = b.state[pb];
+    if (st.done) return;
+    BpArgs<T> a;                                                         // as bp_body (bodies.hpp)
+    a.AB = b.AB + (size_t)pb * N * NX * NM;
+    a.Pm = (st.pw ? b.Pp : b.P) + (size_t)pb * N * NX * NX;   a.pv = (st.pw ? b.pp : b.p) + (size_t)pb * N * NX;
+    a.Pp = (st.pw ? b.P : b.Pp) + (size_t)pb * N * NX * NX;   a.pp = (st.pw ? b.p : b.pp) + (size_t)pb * N * NX;
+    a.H = b.H + (size_t)pb * N * NM * NM;    a.g = b.g + (size_t)pb * N * NM;
+    a.KT = b.KT + (size_t)pb * N * NX * NU;  a.du = b.du + (size_t)pb * N * NU;
+    a.dcur = b.dcur + (size_t)pb * N * NX;
+    a.ApBK = b.ApBK + (size_t)pb * N * NX * NX;  a.Bdu = b.Bdu + (size_t)pb * N * NX;
+    a.xcur = b.xb + ((size_t)pb * 2 + st.cur) * N * NX;
+    a.xprev2 = b.xb + ((size_t)pb * 2 + st.cur2) * N * NX;
+    a.dJexp = b.dJexp + (size_t)pb * 2 * dm.M;
+    a.err = b.err + (size_t)pb * dm.M;
+    a.rho = st.rho;
+    if (bp_box_block<P, T>(s[grp], c, dm, blk, a, b.ucur + (size_t)pb * N * NU, b.ltab + (size_t)pb * 2 * NU)) { if (c == 0) a.err[blk] = 1; }
 }
 
 // k_bp_mq: one wavefront = (problem, block of knots) of a 12-state / 4-control plant on the matrix cores (bp_mq.hpp); grid B M, block 64.  Replaces backPassKern<<<M, ...>>>

@@ -242,7 +242,8 @@ PDDP_HD void mpc_load_body(const Wave& w, MpcScratch<P, T>& s, const Buffers<T>&
                 const T* KTk = KT + NX * NU * kn;
                 T Kdx = 0;
                 for (int c = 0; c < NX; c++) Kdx += KTk[c + r * NX] * s.dx[c];
-                const T uv = u[NU * kn + r] - Kdx;
+                T uv = u[NU * kn + r] - Kdx;
+                if constexpr (IsLimTab<P>::value) uv = control_clamp(uv, b.ltab + (size_t)pb * 2 * NU, r, NU);      // (control limits: the feedback part only, never the caller's or the shifted u)
                 s.u[r] = uv; u[NU * kn + r] = uv;
             }
             wsync();

@@ -299,9 +299,22 @@ template <typename T> PDDP_HD KnotRef<T> goal_at(const RefRows<T>& g, int k) { r
 template <typename B, typename T> struct RefTab;
 template <typename P> struct IsRefTab { static constexpr bool value = false; };
 template <typename B, typename T> struct IsRefTab<RefTab<B, T>> { static constexpr bool value = true; };
+// (LimTab, the layer above RefTab at the end of this chain: the problem's control limit row travels with its goal and reference rows, so the rollouts' control law
+// finds it where it finds the goal)
+template <typename T>
+struct LimRows : RefRows<T> { const T* lim; };
+template <typename B, typename T> struct LimTab;
+template <typename P> struct IsLimTab { static constexpr bool value = false; };
+template <typename B, typename T> struct IsLimTab<LimTab<B, T>> { static constexpr bool value = true; };
+template <typename B, typename T> struct IsRefTab<LimTab<B, T>> { static constexpr bool value = true; };
 template <typename P, typename T>
 PDDP_HD auto problem_goal(const Buffers<T>& b, int pb, int N) {
-    if constexpr (IsRefTab<P>::value) {                             // (control references, below: the goal's base and stride and the reference's)
+    if constexpr (IsLimTab<P>::value) {                             // (control limits, below: RefTab's rows and the problem's limit row)
+        const bool on = b.gflag[pb] != 0, uon = b.uflag[pb] != 0;
+        return LimRows<T>{{on ? b.gtab + (size_t)pb * N * P::NX : b.xGoal + (size_t)pb * P::NX, on ? P::NX : 0,
+                           uon ? b.utab + (size_t)pb * N * P::NU : b.utab - control_ref_pad<T>(P::NU), uon ? P::NU : 0},
+                          b.ltab + (size_t)pb * 2 * P::NU};
+    } else if constexpr (IsRefTab<P>::value) {                             // (control references, below: the goal's base and stride and the reference's)
         const bool on = b.gflag[pb] != 0, uon = b.uflag[pb] != 0;
         return RefRows<T>{on ? b.gtab + (size_t)pb * N * P::NX : b.xGoal + (size_t)pb * P::NX, on ? P::NX : 0,
                           uon ? b.utab + (size_t)pb * N * P::NU : b.utab - control_ref_pad<T>(P::NU), uon ? P::NU : 0};
@@ -362,6 +375,24 @@ struct RefTab : StepTab<B, T> {
 template <typename B, typename T> struct IsDiagTab<RefTab<B, T>> { static constexpr bool value = true; };
 template <typename B, typename T> struct IsGoalTab<RefTab<B, T>> { static constexpr bool value = true; };
 template <typename B, typename T> struct IsStepTab<RefTab<B, T>> { static constexpr bool value = true; };
+
+// ---- control limits of the same plants (pddp_set_control_limits_problems) ----
+// Buffers::ltab is null, or a table [batch][2 NU] of rows lo_0..lo_{NU-1} | hi_0..hi_{NU-1} in the element type; a problem without limits holds -inf.. | +inf.., so
+// there is no flag for a kernel to read and no branch: min(max(u, -inf), +inf) is u bit for bit.  LimTab<B, T> is RefTab<B, T> -- the same records, goals, steps and
+// references -- for the handles that have such a table: the top layer of the chain, a policy of its own, so that the instantiations below it are the ones they always
+// were.  What differs is the control law of the kernels that apply one (k_fp, k_fp_ts, k_fp_cf, k_mpc_load*): u = min(max(ucur - alpha du - K dx, lo), hi).  The
+// backward pass of such a handle is k_bp_box (bp_box.hpp), which reads the table itself and has no policy; setup, initial cost, sweeps, line search and simulators
+// apply no control law and have no LimTab instantiation.
+template <typename B, typename T>
+struct LimTab : RefTab<B, T> {
+    template <typename U> using Rebind = LimTab<typename B::template Rebind<U>, U>;
+};
+template <typename B, typename T> struct IsDiagTab<LimTab<B, T>> { static constexpr bool value = true; };
+template <typename B, typename T> struct IsGoalTab<LimTab<B, T>> { static constexpr bool value = true; };
+template <typename B, typename T> struct IsStepTab<LimTab<B, T>> { static constexpr bool value = true; };
+// control j of the control law, held to the limit row lim = lo | hi (NU entries each)
+template <typename T> PDDP_HD T control_clamp(T u, const T* lim, int j, int NU) { return tmin(tmax(u, lim[j]), lim[NU + j]); }
+
 // the control term's operand of index j at knot k: u_j on every other policy, u_j - U[k][j] on RefTab (nis_knot, k_nis_kb: the lanes that form g themselves)
 template <typename T> PDDP_HD const T* goal_row(const T* g) { return g; }
 template <typename T> PDDP_HD const T* goal_row(const KnotRef<T>& g) { return g.xg; }

@@ -95,6 +95,11 @@ struct SolverBase {
     virtual int set_control_reference_problems(int count, const int* idx, const void* U) = 0;
     virtual int get_control_reference_problems(int count, const int* idx, void* U, int* has) = 0;
     virtual int clear_control_reference_problems(int count, const int* idx) = 0;
+    // control limits of the same plants (control_limit_table.hpp); checked by the handle.  lim in doubles, [count][2 NU]: lo | hi
+    virtual int control_limits_size() const = 0;             // 2 * NU numbers per problem; 0: the plant has no control limits
+    virtual int set_control_limits_problems(int count, const int* idx, const double* lim) = 0;
+    virtual int get_control_limits_problems(int count, const int* idx, double* lim, int* has) = 0;
+    virtual int clear_control_limits_problems(int count, const int* idx) = 0;
     // goal paths of the same plants (goal_path_table.hpp): device-resident references, windowed into the goal table by every call that shifts the previous solution
     virtual int reserve_goal_path(int capacity) = 0;
     virtual int goal_path_capacity() = 0;          // rows per problem; 0 before the reserve

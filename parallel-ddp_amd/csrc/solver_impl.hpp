@@ -11,6 +11,7 @@
 #include "goal_path_table.hpp"
 #include "horizon_time_table.hpp"
 #include "control_ref_table.hpp"
+#include "control_limit_table.hpp"
 #include "sim_slots.hpp"
 #include "mpc_slots.hpp"
 #include "mpc_record.hpp"
@@ -273,7 +274,8 @@ struct Solver : SolverBase {
     // forward pass: plan_fp_launch (kernel_plan.hpp) resolves what `mode` launches -- in production plan.sweep and plan.fp, the kernels pddp_time_kernels names --, the
     // two switches below launch it.  What is not plan is applied here: the line search's mode, the robot model's variant, the arrays this handle has.
     void launch_fp(hipStream_t s, FpMode mode) {
-        const FpLaunch L = plan_fp_launch(plan, cfg, mode);
+        FpLaunch L = plan_fp_launch(plan, cfg, mode);
+        if (b.ltab && L.sweep == kSweepMapsCf) L.sweep = kSweepCf;      // control limits: k_bp_box composes no maps, the record rollouts' own per-knot sweep reads A - B K / B du
         if (L.cand_stale) cand_stale = true;
         launch_fp_sweep(s, L);
         launch_fp_rollouts(s, L);
@@ -283,7 +285,7 @@ struct Solver : SolverBase {
         if constexpr (P::PLANT != 4 && P::kScalarPlugin && (64 / AA) * P::NX <= 64) {
             const unsigned B = cfg.batch;
             const dim3 grid((B + 64 / AA - 1) / (64 / AA));
-            if (rollouts) with_ref_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B); });
+            if (rollouts) with_lim_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_cf<Q, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B); });
             else hipLaunchKernelGGL((k_sweep_cf<P, INTEG, T, AA>), grid, dim3(64), 0, s, b, dm, cw, dt, (int)B);
         }
     }
@@ -330,10 +332,10 @@ struct Solver : SolverBase {
             break;
         case kFpKernCf: if (cfg.A == 16) launch_cf<16>(s, true); else if (cfg.A == 8) launch_cf<8>(s, true); break;
         case kFpKernTs:           // (the arm has its own families: no thread-serial instantiation of its cooperative bodies)
-            if constexpr (P::PLANT != 4) with_ref_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, L.seed == 2 ? 1 : 0); });
+            if constexpr (P::PLANT != 4) with_lim_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp_ts<Q, INTEG, T>), dim3((B * cfg.A + 63) / 64), dim3(64), 0, s, b, dm, cw, dt, (int)B, L.seed == 2 ? 1 : 0); });
             break;
         case kFpKernCoop:
-            with_ref_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(A_all, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, L.seed); });
+            with_lim_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_fp<Q, INTEG, T>), dim3(A_all, B), dim3(64 * cfg.M), fp_lds, s, b, dm, cw, dt, L.seed); });
             break;
         }
         if constexpr (P::PLANT != 4) { if (L.cand_to_xw && b.xw) hipLaunchKernelGGL((k_cand_to_xw<P, T>), dim3((unsigned)(((size_t)B * cfg.N * cfg.A + 255) / 256)), dim3(256), 0, s, b, dm, (int)B); }
@@ -396,6 +398,10 @@ struct Solver : SolverBase {
     // lean: a sweep of split_sweeps() in front of its call's last kKeepSweeps -- interior cost-to-go slots unwritten for the problems that run on
     void launch_bp(hipStream_t s, int store_candidates, bool fused_hook = false, bool lean = false) {
         const unsigned B = cfg.batch;
+        if constexpr (kDiagCost) {
+            // control limits: whatever plan.bp says, the box-constrained backward pass (bp_box.hpp) -- every cost-to-go slot, A - B K / B du, no sweep maps
+            if (b.ltab) { hipLaunchKernelGGL((k_bp_box<P, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, (int)B); return; }
+        }
         switch (plan.bp) {
         case kBpMfma:
             if constexpr (P::PLANT == 4) {
@@ -499,7 +505,7 @@ struct Solver : SolverBase {
     }
     // production sweeps leave the reference-layout views behind (marked here, not only in launch_fp: a hipGraph REPLAY does not pass through the launch functions)
     void note_sweeps_enqueued() {
-        if (plan.sweep_fused || plan.mq_fused) fs_vars_stale = true;
+        if ((plan.sweep_fused || plan.mq_fused) && !b.ltab) fs_vars_stale = true;      // (k_bp_box writes A - B K / B du)
         if (plan.cf_fp && plan.cf_fp_staged) cand_stale = true;
     }
     int iterate(int sweeps) override {
@@ -673,6 +679,12 @@ struct Solver : SolverBase {
     template <typename F> void with_ref_plant(F&& f) {
         if constexpr (kDiagCost) { if (b.utab) { f(RefTab<P, T>{}); return; } }
         with_step_plant(f);
+    }
+    // the kernels that apply the control law (rollouts, warm start): LimTab<P, T> for a handle with a table of control limits (it always has the other four tables),
+    // with_ref_plant's choice otherwise
+    template <typename F> void with_lim_plant(F&& f) {
+        if constexpr (kDiagCost) { if (b.ltab) { f(LimTab<P, T>{}); return; } }
+        with_ref_plant(f);
     }
     template <typename F> void with_ref_cost_plant(F&& f) {
         if constexpr (kDiagCost) { if (b.utab) { f(RefTab<P, T>{}); return; } }
@@ -977,6 +989,95 @@ struct Solver : SolverBase {
         }
         return 0;
     }
+    // ---- control limits of the same plants (control_limit_table.hpp, plants.hpp LimTab, bp_box.hpp): pddp_set_control_limits_problems / pddp_get_... / pddp_clear_...
+    // A table [batch][2 NU] of rows lo | hi from the first setter call on, every row -inf.. | +inf.. until a problem is named; b.ltab is what the kernels see.  With it
+    // launch_bp launches k_bp_box, the rollouts and the warm start run in their LimTab instantiations (with_lim_plant) and the record rollouts sweep per knot (launch_fp).
+    // A handle with a limit table always has the reference, step, goal and cost tables too (LimTab is layered on RefTab), created through ensure_ref_table.
+    DeviceBuf d_ltab;
+    T* ltab_rows() const { return d_ltab.template as<T>(); }
+    std::vector<T> lim_stage;                      // host rows of the call in flight
+    std::vector<char> lim_has;                     // [batch] which problems have limits (the getter's has; the kernels read rows only)
+    size_t lim_len() const { return (size_t)control_limits_len(NU); }
+    int control_limits_size() const override { return kDiagCost ? (int)lim_len() : 0; }
+    int lim_refuse(const char* who) { return fail(PDDP_EINVAL, std::string(who) + ": control limits belong to the pendulum, cart-pole and quadrotor (plants 1-3)"); }
+    // room for `rows` problems, every row open; the kernels do not see it yet
+    int reserve_lim_table(int rows) {
+        if (int rc = reserve(d_ltab, (size_t)rows * lim_len() * sizeof(T), "hipMalloc failed for the control limits")) return rc;
+        lim_stage.resize((size_t)rows * lim_len());
+        for (int i = 0; i < rows; i++) control_limits_open_row<T>(lim_stage.data() + (size_t)i * lim_len(), NU);
+        hipError_t e = hipMemcpyAsync(d_ltab.ptr, lim_stage.data(), (size_t)rows * lim_len() * sizeof(T), hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);       // (lim_stage is reused by the caller)
+        return e == hipSuccess ? 0 : fail(PDDP_ENODEVICE, std::string("control limits: filling the table failed: ") + hipGetErrorString(e));
+    }
+    // first setter call: the tables below it in the chain if there are none, the limit table; b.ltab; the captured graph goes once (other kernels).  A failed step
+    // releases the limit table again; what ensure_ref_table() created before it stays at its defaults, by the rule written there, and the call can be repeated.
+    int ensure_lim_table() {
+        if (b.ltab) return 0;
+        if constexpr (kDiagCost) {
+            if (int rc = ensure_ref_table()) return rc;
+            if (int rc = reserve_lim_table(cfg.batch)) { d_ltab.release(); return rc; }
+            hipError_t e = hipSuccess;
+            if (fp_lds > 48 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fp<LimTab<P, T>, INTEG, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp_lds);
+            if (e != hipSuccess) { d_ltab.release(); return fail(PDDP_ENODEVICE, std::string("control limits: creating the table failed: ") + hipGetErrorString(e)); }
+            lim_has.assign((size_t)cfg.batch, 0);
+            b.ltab = ltab_rows();
+            drop_graph();
+        }
+        return 0;
+    }
+    // rows (already in lim_stage, [count][2 NU]) for the named problems, on the stream, one synchronisation
+    int lim_rows_upload(const char* who, int count, const int* idx) {
+        const size_t len = lim_len();
+        hipError_t e = hipSuccess;
+        for_each_slot_run(count, idx, [&](int first, int run) {     // contiguous runs of slots in one transfer each; problems that are not named keep theirs
+            if (e == hipSuccess) e = hipMemcpyAsync(ltab_rows() + (size_t)idx[first] * len, lim_stage.data() + (size_t)first * len, (size_t)run * len * sizeof(T), hipMemcpyHostToDevice, stream);
+        });
+        const hipError_t es = hipStreamSynchronize(stream);
+        if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string(who) + ": transfer of rows failed: " + hipGetErrorString(e != hipSuccess ? e : es));
+        return 0;
+    }
+    int set_control_limits_problems(int count, const int* idx, const double* lim) override {
+        if (!kDiagCost) return lim_refuse("pddp_set_control_limits_problems");
+        const std::string complaint = control_limits_complaint<T>(count, idx, lim, cfg.batch, NU);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_set_control_limits_problems: " + complaint);
+        if (int rc = ensure_lim_table()) return rc;
+        lim_stage.resize((size_t)count * lim_len());
+        control_limits_round<T>(lim_stage.data(), lim, count, NU);
+        if (int rc = lim_rows_upload("pddp_set_control_limits_problems", count, idx)) return rc;
+        for (int i = 0; i < count; i++) lim_has[(size_t)idx[i]] = 1;
+        return 0;
+    }
+    int clear_control_limits_problems(int count, const int* idx) override {
+        if (!kDiagCost) return lim_refuse("pddp_clear_control_limits_problems");
+        const std::string complaint = control_limits_complaint<T>(count, idx, nullptr, cfg.batch, NU, false);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_clear_control_limits_problems: " + complaint);
+        if (!b.ltab) return 0;                                      // never had limits: nothing is clamped already
+        lim_stage.resize((size_t)count * lim_len());
+        for (int i = 0; i < count; i++) control_limits_open_row<T>(lim_stage.data() + (size_t)i * lim_len(), NU);
+        if (int rc = lim_rows_upload("pddp_clear_control_limits_problems", count, idx)) return rc;
+        for (int i = 0; i < count; i++) lim_has[(size_t)idx[i]] = 0;
+        return 0;
+    }
+    int get_control_limits_problems(int count, const int* idx, double* lim, int* has) override {
+        if (!kDiagCost) return lim_refuse("pddp_get_control_limits_problems");
+        const std::string complaint = control_limits_complaint<T>(count, idx, lim, cfg.batch, NU, true, false);
+        if (!complaint.empty()) return fail(PDDP_EINVAL, "pddp_get_control_limits_problems: " + complaint);
+        const size_t len = lim_len();
+        lim_stage.resize((size_t)count * len);
+        if (b.ltab) {
+            hipError_t e = hipSuccess;
+            for_each_slot_run(count, idx, [&](int first, int run) {
+                if (e == hipSuccess) e = hipMemcpyAsync(lim_stage.data() + (size_t)first * len, ltab_rows() + (size_t)idx[first] * len, (size_t)run * len * sizeof(T), hipMemcpyDeviceToHost, stream);
+            });
+            const hipError_t es = hipStreamSynchronize(stream);
+            if (e != hipSuccess || es != hipSuccess) return fail(PDDP_ENODEVICE, std::string("pddp_get_control_limits_problems: transfer failed: ") + hipGetErrorString(e != hipSuccess ? e : es));
+        } else {
+            for (int i = 0; i < count; i++) control_limits_open_row<T>(lim_stage.data() + (size_t)i * len, NU);
+        }
+        for (size_t e = 0; e < (size_t)count * len; e++) lim[e] = (double)lim_stage[e];
+        if (has) for (int i = 0; i < count; i++) has[i] = (b.ltab && lim_has[(size_t)idx[i]]) ? 1 : 0;
+        return 0;
+    }
     // ---- goal paths of the same plants (goal_path_table.hpp, k_goal_window in kernels.hpp): pddp_reserve_goal_path / pddp_set_goal_path_problems / ..._cursor_problems / pddp_get_...
     // path[batch][capacity][NX] and a record {len, mode, cursor} per problem on the device, from the reserve on.  The invariant: the block of the goal table of a
     // problem with a path holds the window at its cursor, so nothing that reads a goal knows about paths.  k_goal_window restores it wherever a cursor moves: in the
@@ -1183,6 +1284,12 @@ struct Solver : SolverBase {
         const dim3 grid(cfg.batch), block(V < 0 ? 256 : 512);
         const int tsm = (cfg.ee_cost && cfg.ee_cost_shift) ? 1 : 0;
         if constexpr (kDiagCost) {
+            if (b.ltab) {            // control limits: the feedback part of the warm-start rollout clamps (a handle with limits has a step table too)
+                using Q = LimTab<P, T>;
+                if (from) hipLaunchKernelGGL((k_mpc_load_slots<Q, INTEG, T, V>), grid, block, 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
+                else hipLaunchKernelGGL((k_mpc_load<Q, INTEG, T, V>), grid, block, 0, stream, b, mb, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
+                return;
+            }
             if (b.dtab) {            // per-problem time steps: the warm-start rollout in its StepTab instantiation (the kernel reads no cost: P itself on every other handle)
                 using Q = StepTab<P, T>;
                 if (from) hipLaunchKernelGGL((k_mpc_load_slots<Q, INTEG, T, V>), grid, block, 0, stream, b, mb, *from, d_idx, from_batch, dm, dt, d_xActual, d_shift, clear_vars, full_rollout, d_goal_in, tsm);
@@ -1340,6 +1447,10 @@ struct Solver : SolverBase {
             if (int rc = in.reserve_ref_table(slot_chunk())) { in.d_utab.release(); in.d_uflag.release(); return rc; }      // (no half-made table stays behind, as in ensure_ref_table)
             in.b.utab = in.utab_rows(); in.b.uflag = in.uflag_rows();
         }
+        if (b.ltab && !in.b.ltab) {                                  // control limits: the same, one row per slot of the chunk
+            if (int rc = in.reserve_lim_table(slot_chunk())) { in.d_ltab.release(); return rc; }
+            in.b.ltab = in.ltab_rows();
+        }
         if (!b.ABc) { in.b.ABc = nullptr; in.b.Hc = nullptr; }      // the handle left the compact layouts (ab_keep_reference_layout): so does its intake
         return ensure_slot_idx();
     }
@@ -1388,6 +1499,10 @@ struct Solver : SolverBase {
             const size_t ub = ref_len() * sizeof(T);
             if (!slot_add(fetch, in.utab_rows(), utab_rows(), ub, ub, ub, kSlotCopy) || !slot_add(fetch, in.uflag_rows(), uflag_rows(), sizeof(int), sizeof(int), sizeof(int), kSlotCopy))
                 return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
+        }
+        if (b.ltab) {                                                // ... and their control limit rows
+            const size_t lb = lim_len() * sizeof(T);
+            if (!slot_add(fetch, in.ltab_rows(), ltab_rows(), lb, lb, lb, kSlotCopy)) return fail(PDDP_EINVAL, "pddp_load_problems: internal error (slot table)");
         }
         const size_t N = cfg.N;
         const int C = slot_chunk();
@@ -1452,9 +1567,9 @@ struct Solver : SolverBase {
         const bool st = b.dtab != nullptr;
         const bool ut = b.utab != nullptr;
         const MpcSlotSide<T> is{b.cwt ? in.cwt_rows() : nullptr, in.d_xActual, in.d_goal_in, in.d_shift, gt ? in.gtab_rows() : nullptr, gt ? in.gflag_rows() : nullptr, st ? in.dtab_rows() : nullptr,
-                                ut ? in.utab_rows() : nullptr, ut ? in.uflag_rows() : nullptr},
+                                ut ? in.utab_rows() : nullptr, ut ? in.uflag_rows() : nullptr, b.ltab ? in.ltab_rows() : nullptr},
                              hs{b.cwt ? cwt_rows() : nullptr, d_xActual, d_goal_in, d_shift, gt ? gtab_rows() : nullptr, gt ? gflag_rows() : nullptr, st ? dtab_rows() : nullptr,
-                                ut ? utab_rows() : nullptr, ut ? uflag_rows() : nullptr};
+                                ut ? utab_rows() : nullptr, ut ? uflag_rows() : nullptr, b.ltab ? ltab_rows() : nullptr};
         return mpc_slot_tables<NX, NU, T>(in_t, out_t, in.b, in.mb, is, b, mb, hs, cfg.N, cfg.M, cfg.A, cfg.max_iter, cfg.ee_cost, table_record_len());
     }
     // pddp_mpc_slots_profile (measurement): HIP events around the in stage (movers + load kernel), the cycle and the out stage of every chunk
@@ -1586,6 +1701,7 @@ struct Solver : SolverBase {
         else if (phase == PDDP_PHASE_BP_FUSED || phase == PDDP_PHASE_SWEEP_FUSED) {
             // the production sweep path under teacher forcing: the matrix-core backward pass composes the segment maps (and writes every cost-to-go slot, not
             // A - B K / B du); then k_sweep_maps alone -- the candidates' segment start states land in xs
+            if (b.ltab) return fail(PDDP_EINVAL, "PDDP_PHASE_BP_FUSED / _SWEEP_FUSED: a handle with control limits composes no sweep maps (k_bp_box writes A - B K / B du and its family's per-knot sweep reads them)");
             if (!plan.sweep_fused && !plan.mq_fused) return fail(PDDP_EINVAL, "PDDP_PHASE_BP_FUSED / _SWEEP_FUSED: this handle's selection has no fused sweep (matrix-core backward pass -- the KUKA arm's, or the 12-state plants' with the record rollouts --, M > 1, no kernels.sweep override)");
             if (phase == PDDP_PHASE_BP_FUSED) launch_bp(stream, 1, true);
             else launch_fp(stream, kFpHookFusedSweep);

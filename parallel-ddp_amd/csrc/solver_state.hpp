@@ -78,6 +78,7 @@ struct Buffers {
     const T* dtab = nullptr;   // [B] per-problem time steps of the same plants (plants.hpp StepTab, problem_dt); null: every problem integrates with the kernel argument dt
     const T* utab = nullptr;   // [B][N][m] control references of the same plants (plants.hpp RefTab), control_ref_pad<T>(m) zeros in front of row 0; null: every control term is taken on u itself
     const int* uflag = nullptr;      // [B] with utab: 1 = the problem's control term reads u_k - utab[b][k], 0 = it reads the zero row in front of the table
+    const T* ltab = nullptr;   // [B][2 m] control limits of the same plants (plants.hpp LimTab, bp_box.hpp): lo_0..lo_{m-1} | hi_0..hi_{m-1}, -inf.. | +inf.. for a problem without limits; null: no control is limited
 };
 
 // Buffers::utab: the zero row an unflagged problem reads sits in FRONT of the table, control_ref_pad<T>(m) elements -- whole 16-byte pieces, so that the rows behind it

@@ -452,6 +452,42 @@ class Solver:
         self.lib.pddp_clear_control_reference_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._chk(self.lib.pddp_clear_control_reference_problems(self.h, idx.size, _p(idx)))
 
+    # ---- control limits (pendulum, cart-pole, quadrotor): lo <= u_k <= hi on every running knot, box-constrained backward pass + clamped rollouts
+    def control_limits_size(self):
+        """pddp_control_limits_size: 2 * m numbers per problem, lo_0..lo_{m-1} | hi_0..hi_{m-1}; plants 1-3 only."""
+        self.lib.pddp_control_limits_size.argtypes = [C.c_void_p]
+        rc = self.lib.pddp_control_limits_size(self.h)
+        if rc <= 0:
+            self._chk(rc if rc else -1)
+        return rc
+
+    def set_control_limits(self, idx, lim):
+        """pddp_set_control_limits_problems: row i of lim (len(idx) x 2m doubles, lo | hi; -inf / +inf: no bound on that side) for slot idx[i].  In force for the
+        following loads, solves and control cycles; the other slots keep theirs."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        lim = np.ascontiguousarray(lim, dtype=np.float64).ravel()
+        if lim.size != idx.size * self.control_limits_size():
+            raise PddpError(f"set_control_limits: {idx.size} slots need {idx.size * self.control_limits_size()} numbers ({self.control_limits_size()} per row), got {lim.size}")
+        self.lib.pddp_set_control_limits_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_set_control_limits_problems(self.h, idx.size, _p(idx), _p(lim)))
+
+    def get_control_limits(self, idx):
+        """pddp_get_control_limits_problems: (lim [len(idx)][2m] float64, has [len(idx)] int32).  has[i] = 1: slot idx[i] has limits and lim[i] is its row as
+        rounded to the handle's element type; 0: it has none and lim[i] is -inf.. | +inf..."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        lim = np.zeros((idx.size, 2 * self.m), np.float64)
+        has = np.zeros(idx.size, np.int32)
+        self.control_limits_size()                        # (raises for plants 4 and 5 before the shapes above mean anything)
+        self.lib.pddp_get_control_limits_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.pddp_get_control_limits_problems(self.h, idx.size, _p(idx), _p(lim), _p(has)))
+        return lim, has
+
+    def clear_control_limits(self, idx):
+        """pddp_clear_control_limits_problems: the named slots are unlimited again; a no-op on a handle that never had a table."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        self.lib.pddp_clear_control_limits_problems.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(self.lib.pddp_clear_control_limits_problems(self.h, idx.size, _p(idx)))
+
     # ---- per-problem horizon times (pendulum, cart-pole, quadrotor)
     def set_horizon_time_problems(self, idx, times):
         """pddp_set_horizon_time_problems: times[i] seconds (len(idx) doubles) is the horizon time of slot idx[i]; its step is T(times[i] / (N - 1)), what a handle created
