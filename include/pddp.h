@@ -439,11 +439,13 @@ int pddp_clear_control_reference_problems(pddp_handle h, int count, const int* i
  * problems that are not named keep theirs; the first setter call gives the handle a device table [batch][2 m] in its element type -- and, where it has none, the
  * reference, step, goal and cost tables the way the first pddp_set_control_reference_problems call creates them -- and drops the captured sweep graph once; later
  * calls only write rows (on the solver's stream, one synchronisation before the call returns).  A handle that never calls the setter launches exactly the kernels and
- * arguments it launches without these entry points.  A handle WITH a table launches k_bp_box (csrc/bp_box.hpp) for its backward pass whatever its kernel selection
- * says -- a full-device quadrotor handle gives up the matrix-core backward pass and the fused sweep maps --, and pddp_time_kernels keeps reporting the SELECTION's
- * name in slot 0 for it, and where the selection's sweep applies composed maps (k_sweep_maps_cf) it keeps that name in slot 1 while k_sweep_cf runs.
- * pddp_run_phase(PDDP_PHASE_BP) launches k_bp_box on such a handle, PDDP_PHASE_BP_COOP the cooperative kernel without limits; PDDP_PHASE_BP_FUSED and
- * PDDP_PHASE_SWEEP_FUSED are refused with PDDP_EINVAL (there are no maps).
+ * arguments it launches without these entry points.  A handle WITH a table whose selection resolves the backward pass to k_bp_mq (the quadrotor on the matrix
+ * cores) and whose cost Hessian is the plant's own keeps that kernel, in its box-constrained instantiations (csrc/bp_mq.hpp BOX), and the fused sweep maps
+ * (k_sweep_maps_cf); pddp_run_phase(PDDP_PHASE_BP / _BP_FUSED / _SWEEP_FUSED) work on it as without a table.  Every other handle WITH a table -- any other selection,
+ * or a Hessian overridden through pddp_set_array("H") -- launches k_bp_box (csrc/bp_box.hpp) for its backward pass whatever its kernel selection says;
+ * pddp_time_kernels keeps reporting the SELECTION's name in slot 0 for it, and where the selection's sweep applies composed maps (k_sweep_maps_cf) it keeps that
+ * name in slot 1 while k_sweep_cf runs.  pddp_run_phase(PDDP_PHASE_BP) launches k_bp_box on such a handle, PDDP_PHASE_BP_COOP the cooperative kernel without limits;
+ * PDDP_PHASE_BP_FUSED and PDDP_PHASE_SWEEP_FUSED are refused with PDDP_EINVAL (there are no maps).
  * pddp_load_problems, pddp_mpc_solve_problems and pddp_mpc_load_problems run the named slots with their own rows; nothing is written back.
  * pddp_get_control_limits_problems returns the stored rows (as rounded) and has[i] = 1 for a problem with limits; for a problem without (and for every problem before
  * the first setter call) -inf.. | +inf.. and has[i] = 0.  has may be NULL.  pddp_clear_control_limits_problems: the named problems are unlimited again; on a handle that

@@ -19,6 +19,7 @@
 // costs take the instantiation that reads H_k.  k_bp_cl stays selectable (pddp_config.kernels.cf_bp = cl): it is bit for bit the cooperative kernel.
 #pragma once
 
+#include "bp_box.hpp"
 #include "bp_mfma.hpp"
 #include "plants.hpp"
 
@@ -48,6 +49,7 @@ template <typename T> __device__ __forceinline__ mx4t<T> mq_controls(const mx4t<
 #endif
 constexpr int kMqStage = 160;                  // one staged pair: a 12 x 12 block (144) + its 12-vector right behind it, padded to whole 16-byte pieces
 constexpr int kMqLds = 64 + 2 * kMqStage + 64; // elements per wave: Huu 16 | cofactors 16 | inverse 16 | boundary p 16 | staging [P | p] | staging [A - B K | B du] | [A B]'p 16 | Hxu 48
+constexpr int kMqBoxLds = 24;                  // ... of a BOX instantiation, behind those: the problem's limit row 8 | the knot's Qu 4 | its box for du 8 | du 4
 
 // Per-knot memory operations of the loop.  float: BUFFER instructions -- a wave-uniform resource per array, the knot's position a scalar byte offset, the lane's share a
 // loop-invariant 32-bit vector offset (no 64-bit vector address arithmetic per access: as in bp_mfma.hpp, that arithmetic was a third of the first cut's vector
@@ -89,7 +91,18 @@ template <> struct MqMem<double> {
 // instructions per knot against 624 of the knot's ~2400 bytes of memory traffic and the whole per-knot linear sweep (k_sweep_cf: it read those bytes back);
 // Psi' goes to b.segmap[problem][block] and k_sweep_maps_cf (kernels.hpp) finishes.  The last block's segment has no boundary behind it: it composes nothing.
 // Same mathematics as bp_mfma.hpp's kMxFuseSweep (the arm's production path since round 3); A - B K | B du stay available through pddp_refresh_reference_views.
-template <typename P, typename T, bool FS, bool DIAGH, bool FUSE = false>
+// BOX: hard control limits lo <= u_k <= hi (b.ltab; the mathematics of bp_box.hpp).  Everything behind the gains is written in the form that holds
+// for ANY K, du, so only those two change at a knot whose unconstrained step leaves its box  ucur_k - hi <= du <= ucur_k - lo:
+//   hot path   the adjugate inverse with its det > 0 test on the FULL Huu (the rho retry) and Kp = Huu^-1 [Hux | Qu] as without limits; the vector-column lane of control a
+//              tests du(a) against the box it forms from ucur_k(a) -- fetched with the knot's operands -- and the problem's limit row in LDS; one ballot.  No control
+//              outside: nothing else happens, the knot is BOX = false's bit for bit (and so is every knot of a problem whose row is -inf.. | +inf..).
+//   cold path  Qu, the box and du go through LDS next to Huu (ldsU[i + 4 j] = Huu(i, j): box_qp's Q[j * NU + i]); EVERY lane runs the active-set walk box_qp on the
+//              same numbers, so the clamped set and the factors of Quu_ff are uniform over the wave without an exchange; lane (g = b, control column a) solves for
+//              e_b and keeps entry a: Z = Quu_ff^-1 embedded in 4 x 4, zero rows and columns for the clamped controls, written where Huu^-1 goes (ldsI).  Kp = Z [Hux | .]
+//              is ONE more matrix instruction -- zero rows of K for the clamped controls, Quu_ff^-1 Qux_f for the free ones -- and its vector column takes box_qp's du
+//              (Z Qu lacks the - Quu_fc du_c term).  The walk's ~40 values live in that scope only: its results leave through LDS.
+//              A cap hit or a failed pivot is err[block] = 1, like the det test.
+template <typename P, typename T, bool FS, bool DIAGH, bool FUSE = false, bool BOX = false>
 __device__ void mq_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, const CostWeights<T>& cw, int pb, int blk) {
     static_assert(!FUSE || FS, "segment maps exist with M > 1 only");
     static_assert(P::NX == 12 && P::NU == 4, "matrix-core backward pass of the 12-state / 4-control plants");
@@ -119,6 +132,12 @@ __device__ void mq_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, const C
     int ks = NBk * (blk + 1) - 1, iterCount;
     mx4 Pa = zero;                                                           // [P | p]: P(3g + r, sc), p in the vector column
     const MqMem<T> mAB(AB), mH(H), mG(gg), mKT(KT), mDu(du), mF(ApBK), mBd(Bdu), mP(Pw), mp(pw);
+    const MqMem<T> mU(BOX ? b.ucur + knot0 * NU : nullptr);
+    T* const ldsLim = lds + kMqLds; T* const ldsQ = ldsLim + 2 * NU; T* const ldsB = ldsQ + NU; T* const ldsD = ldsB + 2 * NU;
+    if constexpr (BOX) {                                                     // the problem's limit row lo | hi: once, in front of the knot loop
+        if (lane < 2 * NU) ldsLim[lane] = b.ltab[(size_t)pb * 2 * NU + lane];
+        wsync();
+    }
     // loop-invariant element offsets of this lane inside a knot's blocks
     const unsigned oCol = (unsigned)((cx ? sc : NX + cg) * NX + 3 * g), oBt = (unsigned)((NX + g) * NX + sc), oG3 = (unsigned)(3 * g), oGu = (unsigned)(NX + g);
     const unsigned oKT = (unsigned)(sc + NX * g), oP = (unsigned)(sc * NX + 3 * g), oHcol = (unsigned)((cx ? sc : NX + cg) * NM), oHxu = (unsigned)((NX + g) * NM + sc);
@@ -175,7 +194,7 @@ __device__ void mq_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, const C
     // A knot's operands as they come from memory: this lane's three elements of its column of [A B], B(sc, g), g_x, g_u (and, read from H_k, its column's pieces).
     // PDDP_MQ_PREFETCH: requested ONE KNOT AHEAD -- the loads of knot k - 1 are in flight while knot k's products run (the compiler cannot hoist them itself past the
     // knot's stores); without it every knot begins with a round trip to memory that only the other resident waves hide.
-    struct Ops { T v[3], bt, gx[3], gu, hc[3], hu, hxu; };
+    struct Ops { T v[3], bt, gx[3], gu, hc[3], hu, hxu, uc; };              // (uc: ucur_k(g), BOX)
     constexpr int PF = FUSE ? PDDP_MQ_FUSE_PREFETCH : PDDP_MQ_PREFETCH;    // 1: everything one knot ahead; 2: [A B] one knot ahead, the gradient at the knot; 0: nothing ahead
     auto fetch_g = [&](int k, Ops& o) { const unsigned sG = (unsigned)k * NM; mG.ld3(o.gx, oG3, sG); o.gu = mG.ld1(oGu, sG); };
     auto fetch = [&](int k, Ops& o) {
@@ -183,6 +202,7 @@ __device__ void mq_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, const C
         mAB.ld3(o.v, oCol, sAB);
         o.bt = FS ? mAB.ld1(oBt, sAB) : T(0);                                // B(sc, g)   (state-column lanes)
         if (PF != 2) fetch_g(k, o);
+        if constexpr (BOX) o.uc = mU.ld1((unsigned)g, (unsigned)k * NU);
         if (!DIAGH) {                                                        // Hcost(kx, ky) | Hcost(12 + b, kx) | Hcost(kx, 12 + b) | Hcost(12 + a, 12 + b): column-major H_k
             const unsigned sH = (unsigned)k * SZH;
             mH.ld3(o.hc, oHcol + oG3, sH);                                   // this lane's column of H_k
@@ -267,7 +287,30 @@ __device__ void mq_bp_block(T* lds, const Buffers<T>& b, const Dims& dm, const C
         if (cu) InvT[3] = ldsI[cg + 4 * g];
         wsync();
         // ---- gains (computeKTdu :208-220): K(a, kx) | du(a), row a = lane group
-        const mx4 Kp = mq_controls<T>(InvT, Hux, zero);
+        mx4 Kp = mq_controls<T>(InvT, Hux, zero);
+        if constexpr (BOX) {
+            const T blo = o.uc - ldsLim[NU + g], bhi = o.uc - ldsLim[g];     // the knot's box for du(g)
+            if (__builtin_amdgcn_ballot_w64(cv && (Kp[3] < blo || Kp[3] > bhi)) != 0) {      // (uniform over the wave)
+                if (cv) { ldsQ[g] = Hux[3]; ldsB[g] = blo; ldsB[NU + g] = bhi; ldsD[g] = Kp[3]; }
+                wsync();
+                {
+                    T x[NU], L[NU * NU], Ld[NU], e[NU], y[NU];
+                    unsigned cm = 0;
+                    PDDP_BOX_UNROLL for (int i = 0; i < NU; i++) x[i] = ldsD[i];
+                    if (box_qp<T, NU>(ldsU, ldsQ, ldsB, ldsB + NU, x, cm, L, Ld)) { if (lane == 0) b.err[(size_t)pb * dm.M + blk] = 1; return; }
+                    PDDP_BOX_UNROLL for (int i = 0; i < NU; i++) e[i] = i == g ? T(1) : T(0);
+                    box_solve<T, NU>(L, Ld, e, y);
+                    const T z = (((cm >> cg) | (cm >> g)) & 1u) ? T(0) : cg == 0 ? y[0] : cg == 1 ? y[1] : cg == 2 ? y[2] : y[3];
+                    if (cu) ldsI[cg + 4 * g] = z;
+                    if (cv) ldsD[g] = g == 0 ? x[0] : g == 1 ? x[1] : g == 2 ? x[2] : x[3];
+                }
+                wsync();
+                if (cu) InvT[3] = ldsI[cg + 4 * g];
+                Kp = mq_controls<T>(InvT, Hux, zero);
+                if (cv) Kp[3] = ldsD[g];
+                wsync();
+            }
+        }
         if (cx) mKT.st1(Kp[3], oKT, (unsigned)ks * (NX * NU));
         else if (cv) mDu.st1(Kp[3], (unsigned)g, (unsigned)ks * NU);
         // T1(kx, b) = sum_a K(a, kx) Huu(a, b) - Hxu(kx, b) as [b][kx]; its vector column is Huu' du

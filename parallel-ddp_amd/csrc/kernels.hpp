@@ -928,7 +928,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) ==
 }
 
 // k_bp_box: the backward pass of a handle with control limits (bp_box.hpp): 16 lanes = (problem, block of knots), lane = column of [A B] / H, the box step of every knot
-// solved redundantly in the unit's registers; grid ceil(B M / 4), block 64.  Not a plan choice: launch_bp launches it wherever Buffers::ltab exists.
+// solved redundantly in the unit's registers; grid ceil(B M / 4), block 64.  Not a plan choice: launch_bp launches it wherever Buffers::ltab exists, except where the
+// plan is k_bp_mq with the plant's own cost Hessian -- that handle's limits run in k_bp_mq's BOX instantiations (Solver::limits_on_mq).
 template <typename P, typename T>
 __global__ __launch_bounds__(64) void k_bp_box(Buffers<T> b, Dims dm, int batch) {
     __shared__ BpBoxLds<P, T> s[4];
@@ -962,13 +963,22 @@ __global__ __launch_bounds__(64) void k_bp_box(Buffers<T> b, Dims dm, int batch)
 #ifndef PDDP_MQ_FUSE_WAVES
 #define PDDP_MQ_FUSE_WAVES 6 // ... and the instantiations that compose the sweep maps (four more live registers: six waves without the operand prefetch, PDDP_MQ_FUSE_PREFETCH in bp_mq.hpp)
 #endif
-template <typename P, typename T, bool DIAGH, bool FUSE = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? (FUSE ? PDDP_MQ_FUSE_WAVES : PDDP_MQ_WAVES) : 3, sizeof(T) == 4 ? (FUSE ? PDDP_MQ_FUSE_WAVES : PDDP_MQ_WAVES) : 3))) void k_bp_mq(Buffers<T> b, Dims dm, CostWeights<T> cw, int batch) {
-    __shared__ __attribute__((aligned(16))) T lds[kMqLds];
+#ifndef PDDP_MQ_BOX_WAVES
+#define PDDP_MQ_BOX_WAVES 3  // ... and the instantiations with control limits (BOX, float): the knot's live values stay in registers across the cold path's active-set walk -- 134 / 137
+                             // registers, no scratch; compiled for four waves the walk spills 3 / 15 values, for five 90 (profiles/control_limits.md)
+#endif
+#ifndef PDDP_MQ_BOX_WAVES64
+#define PDDP_MQ_BOX_WAVES64 2 // ... (BOX, double: 253 registers, no scratch)
+#endif
+template <typename T, bool FUSE, bool BOX> constexpr int mq_waves() { return sizeof(T) == 4 ? (BOX ? PDDP_MQ_BOX_WAVES : FUSE ? PDDP_MQ_FUSE_WAVES : PDDP_MQ_WAVES) : (BOX ? PDDP_MQ_BOX_WAVES64 : 3); }
+// BOX: a handle with control limits whose plan is this kernel and whose cost Hessian is the plant's own (launch_bp) -- the box step of bp_mq.hpp, b.ltab and b.ucur read
+template <typename P, typename T, bool DIAGH, bool FUSE = false, bool BOX = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(mq_waves<T, FUSE, BOX>(), mq_waves<T, FUSE, BOX>()))) void k_bp_mq(Buffers<T> b, Dims dm, CostWeights<T> cw, int batch) {
+    __shared__ __attribute__((aligned(16))) T lds[kMqLds + (BOX ? kMqBoxLds : 0)];
     const int inst = blockIdx.x;
     if (inst >= batch * dm.M) return;
-    if (dm.M > 1) mq_bp_block<P, T, true, DIAGH, FUSE>(lds, b, dm, cw, inst / dm.M, inst % dm.M);
-    else mq_bp_block<P, T, false, DIAGH>(lds, b, dm, cw, inst / dm.M, inst % dm.M);
+    if (dm.M > 1) mq_bp_block<P, T, true, DIAGH, FUSE, BOX>(lds, b, dm, cw, inst / dm.M, inst % dm.M);
+    else mq_bp_block<P, T, false, DIAGH, false, BOX>(lds, b, dm, cw, inst / dm.M, inst % dm.M);
 }
 
 // k_sweep_maps_cf: grid ceil(B / 4), block 64 -- 16 lanes per problem, lane l < NX owns entry l.  The forward sweep from the per-segment maps k_bp_mq<.., FUSE> composed:

@@ -381,7 +381,7 @@ template <typename B, typename T> struct IsStepTab<RefTab<B, T>> { static conste
 // there is no flag for a kernel to read and no branch: min(max(u, -inf), +inf) is u bit for bit.  LimTab<B, T> is RefTab<B, T> -- the same records, goals, steps and
 // references -- for the handles that have such a table: the top layer of the chain, a policy of its own, so that the instantiations below it are the ones they always
 // were.  What differs is the control law of the kernels that apply one (k_fp, k_fp_ts, k_fp_cf, k_mpc_load*): u = min(max(ucur - alpha du - K dx, lo), hi).  The
-// backward pass of such a handle is k_bp_box (bp_box.hpp), which reads the table itself and has no policy; setup, initial cost, sweeps, line search and simulators
+// backward pass of such a handle is k_bp_box (bp_box.hpp) or a BOX instantiation of k_bp_mq (bp_mq.hpp), which read the table themselves and have no policy; setup, initial cost, sweeps, line search and simulators
 // apply no control law and have no LimTab instantiation.
 template <typename B, typename T>
 struct LimTab : RefTab<B, T> {

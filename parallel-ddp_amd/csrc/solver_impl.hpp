@@ -275,7 +275,7 @@ struct Solver : SolverBase {
     // two switches below launch it.  What is not plan is applied here: the line search's mode, the robot model's variant, the arrays this handle has.
     void launch_fp(hipStream_t s, FpMode mode) {
         FpLaunch L = plan_fp_launch(plan, cfg, mode);
-        if (b.ltab && L.sweep == kSweepMapsCf) L.sweep = kSweepCf;      // control limits: k_bp_box composes no maps, the record rollouts' own per-knot sweep reads A - B K / B du
+        if (b.ltab && !limits_on_mq() && L.sweep == kSweepMapsCf) L.sweep = kSweepCf;      // control limits on k_bp_box: it composes no maps, the record rollouts' own per-knot sweep reads A - B K / B du
         if (L.cand_stale) cand_stale = true;
         launch_fp_sweep(s, L);
         launch_fp_rollouts(s, L);
@@ -396,11 +396,18 @@ struct Solver : SolverBase {
     }
     // fused_hook: pddp_run_phase(PDDP_PHASE_BP_FUSED), the hook's backward pass composing the sweep maps as production's does
     // lean: a sweep of split_sweeps() in front of its call's last kKeepSweeps -- interior cost-to-go slots unwritten for the problems that run on
+    // "this handle's limits run on k_bp_mq": a limit table, the plan's backward pass the matrix-core kernel of the 12-state plants, and the plant's own diagonal cost
+    // Hessian (launch_bp's dh) -- the BOX instantiations of bp_mq.hpp, the sweep maps kept.  Evaluated per launch: pddp_set_array("H") changes it (and drops the graph).
+    bool limits_on_mq() const {
+        if constexpr (kDiagCost && P::NX == 12 && P::NU == 4) return b.ltab && plan.bp == kBpMq && !P::kPluginCost && !h_overridden;
+        else return false;
+    }
     void launch_bp(hipStream_t s, int store_candidates, bool fused_hook = false, bool lean = false) {
         const unsigned B = cfg.batch;
         if constexpr (kDiagCost) {
-            // control limits: whatever plan.bp says, the box-constrained backward pass (bp_box.hpp) -- every cost-to-go slot, A - B K / B du, no sweep maps
-            if (b.ltab) { hipLaunchKernelGGL((k_bp_box<P, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, (int)B); return; }
+            // control limits: the box-constrained backward pass (bp_box.hpp) -- every cost-to-go slot, A - B K / B du, no sweep maps -- whatever plan.bp says, except
+            // where the limits run on k_bp_mq (below)
+            if (b.ltab && !limits_on_mq()) { hipLaunchKernelGGL((k_bp_box<P, T>), dim3((B * cfg.M + 3) / 4), dim3(64), 0, s, b, dm, (int)B); return; }
         }
         switch (plan.bp) {
         case kBpMfma:
@@ -424,6 +431,13 @@ struct Solver : SolverBase {
                 const bool fu = plan.mq_fused && (!store_candidates || fused_hook);      // (the phase hook's backward pass writes A - B K / B du: its sweep is teacher-forced from them)
                 const bool dh = !P::kPluginCost && !h_overridden;   // the plant's own diagonal cost Hessian: not read
                 // (only the instantiations that take the running knots' Hessian from the weights differ with a table of diagonal records: the others read H)
+                if constexpr (kDiagCost) {
+                    if (b.ltab) {                                   // limits_on_mq(): dh holds
+                        if (fu) with_weight_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
+                        else with_weight_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, false, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
+                        break;
+                    }
+                }
                 if (dh && fu) with_weight_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
                 else if (dh) with_weight_plant([&](auto pl) { using Q = decltype(pl); hipLaunchKernelGGL((k_bp_mq<Q, T, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B); });
                 else if (fu) hipLaunchKernelGGL((k_bp_mq<P, T, false, true>), dim3(B * cfg.M), dim3(64), 0, s, b, dm, cw, (int)B);
@@ -505,7 +519,7 @@ struct Solver : SolverBase {
     }
     // production sweeps leave the reference-layout views behind (marked here, not only in launch_fp: a hipGraph REPLAY does not pass through the launch functions)
     void note_sweeps_enqueued() {
-        if ((plan.sweep_fused || plan.mq_fused) && !b.ltab) fs_vars_stale = true;      // (k_bp_box writes A - B K / B du)
+        if ((plan.sweep_fused || plan.mq_fused) && (!b.ltab || limits_on_mq())) fs_vars_stale = true;      // (k_bp_box writes A - B K / B du)
         if (plan.cf_fp && plan.cf_fp_staged) cand_stale = true;
     }
     int iterate(int sweeps) override {
@@ -991,7 +1005,7 @@ struct Solver : SolverBase {
     }
     // ---- control limits of the same plants (control_limit_table.hpp, plants.hpp LimTab, bp_box.hpp): pddp_set_control_limits_problems / pddp_get_... / pddp_clear_...
     // A table [batch][2 NU] of rows lo | hi from the first setter call on, every row -inf.. | +inf.. until a problem is named; b.ltab is what the kernels see.  With it
-    // launch_bp launches k_bp_box, the rollouts and the warm start run in their LimTab instantiations (with_lim_plant) and the record rollouts sweep per knot (launch_fp).
+    // launch_bp launches k_bp_box (k_bp_mq's BOX instantiations where limits_on_mq()), the rollouts and the warm start run in their LimTab instantiations (with_lim_plant) and the record rollouts sweep per knot (launch_fp; from the maps where limits_on_mq()).
     // A handle with a limit table always has the reference, step, goal and cost tables too (LimTab is layered on RefTab), created through ensure_ref_table.
     DeviceBuf d_ltab;
     T* ltab_rows() const { return d_ltab.template as<T>(); }
@@ -1701,7 +1715,7 @@ struct Solver : SolverBase {
         else if (phase == PDDP_PHASE_BP_FUSED || phase == PDDP_PHASE_SWEEP_FUSED) {
             // the production sweep path under teacher forcing: the matrix-core backward pass composes the segment maps (and writes every cost-to-go slot, not
             // A - B K / B du); then k_sweep_maps alone -- the candidates' segment start states land in xs
-            if (b.ltab) return fail(PDDP_EINVAL, "PDDP_PHASE_BP_FUSED / _SWEEP_FUSED: a handle with control limits composes no sweep maps (k_bp_box writes A - B K / B du and its family's per-knot sweep reads them)");
+            if (b.ltab && !limits_on_mq()) return fail(PDDP_EINVAL, "PDDP_PHASE_BP_FUSED / _SWEEP_FUSED: a handle with control limits on k_bp_box composes no sweep maps (k_bp_box writes A - B K / B du and its family's per-knot sweep reads them)");
             if (!plan.sweep_fused && !plan.mq_fused) return fail(PDDP_EINVAL, "PDDP_PHASE_BP_FUSED / _SWEEP_FUSED: this handle's selection has no fused sweep (matrix-core backward pass -- the KUKA arm's, or the 12-state plants' with the record rollouts --, M > 1, no kernels.sweep override)");
             if (phase == PDDP_PHASE_BP_FUSED) launch_bp(stream, 1, true);
             else launch_fp(stream, kFpHookFusedSweep);
